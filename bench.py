@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the DRR render path on MI355X: DRRs/s, forward + backward (pose and voxel gradient).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch: render B poses of a 512^3 volume onto a 256^2
@@ -12,8 +12,11 @@ fwd+bwd, 256x256 detector, batch_size=116 on 1xMI355X"); synthetic seeded phanto
 scaling; the unit -- a pose -- is independent) and the rendered DRRs are all-gathered over RCCL.
 
 Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel, timed live with HIP events
-on the launch stream; `cpu_baseline` is the oracle (the torch-ops restatement of the reference's CPU
-render path) timed on this host on a bounded sample.
+on the launch stream.  A plain run sets up, warms up, times the K steps and prints the line; --full adds
+what the headline does not need: the secondary legs (`variants`), `cpu_baseline` (the oracle -- the
+torch-ops restatement of the reference's CPU render path -- timed on this host on a bounded sample) and,
+at N > 1, the step timed without the voxel-gradient exchange.  --dump-outputs DIR writes what the last
+timed step computed (see dump_outputs) for comparing two builds output for output.
 """
 import argparse
 import json
@@ -22,6 +25,7 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -158,8 +162,9 @@ def render_leg(dev, subject, renderer, voxel_grad, rot0, xyz0, H, delx, n_points
     renderers.PROFILER = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step()
+    img = step()   # (the last step's DRRs are kept: --dump-outputs)
     torch.cuda.synchronize()
     if exchange is not None:
         dist.barrier()
@@ -221,13 +226,35 @@ def render_leg(dev, subject, renderer, voxel_grad, rot0, xyz0, H, delx, n_points
         "kernel_ms_per_step": kernel_ms, "bytes_per_unit": bytes_per_unit * (2 if voxel_grad else 1),
     }
     return {"elapsed": elapsed, "ms_per_step": 1e3 * elapsed / steps, "kernels": kernels, "roofline": roofline, "units": units,
-            "step": step, "drr": drr, "spec": spec, "rot": rot, "xyz": xyz, "B": B, "density": density}
+            "step": step, "drr": drr, "spec": spec, "rot": rot, "xyz": xyz, "B": B, "density": density, "img": img.detach()}
 
 
 def leg_summary(leg, B):
     """What a secondary leg contributes to the JSON line: ms per step, DRRs/s, its kernel table and roofline."""
     return {"ms_per_step": leg["ms_per_step"], "DRRs_per_s": B / (leg["ms_per_step"] * 1e-3), "kernels": leg["kernels"],
             "roofline": leg["roofline"]}
+
+
+DUMP_CAPS = {"drr": 8 << 20, "grad_rot": 1 << 20, "grad_xyz": 1 << 20, "grad_density": 4 << 20}   # float32 elements: 56 MB in all
+
+
+def dump_outputs(leg, out_dir):
+    """What a caller of the timed path received from its last step -> out_dir/<name>.npy, float32: the DRRs [B, 1, H, W], d/drot and
+    d/dxyz [B, 3] and d/dvolume.  An array above its cap in DUMP_CAPS is flattened and sampled at sorted indices drawn from a generator
+    seeded with 0 (the indices depend on the array's size alone), saved as <name>_sample.npy: the default run's voxel gradient (512^3)
+    is 4 Mi of its voxels.  From run to run the DRRs and the voxel gradient are the same bits; the pose gradients are float sums
+    whose order varies (about 1e-6 relative at the default size), so compare them with a tolerance."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {"drr": leg["img"], "grad_rot": leg["rot"].grad, "grad_xyz": leg["xyz"].grad, "grad_density": leg["density"].grad}
+    for name, t in arrays.items():
+        if t is None:   # (pose-only backward: no voxel gradient)
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_CAPS[name]:
+            idx = torch.randint(0, t.numel(), (DUMP_CAPS[name],), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(out / f"{name}.npy", t.float().cpu().numpy())
 
 
 def main():
@@ -276,7 +303,15 @@ def main():
                     help="allocate the exact tensors of the N-rank step (--gpus N names N; this process is ONE rank), run the rank-local "
                          "part once with the all-gather on a one-rank group of the chosen backend, check the gathered block against "
                          "the render, print a JSON report and exit: the first 8-GPU run then measures instead of debugging")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the secondary legs (see --no-variants), the CPU baseline (see "
+                         "--no-cpu-baseline) and, at N > 1, the step timed without the voxel-gradient exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (DRRs, pose gradients, a seeded sample of the voxel "
+                         "gradient) to DIR/<name>.npy in float32, at most 64 MB in all; rank 0's outputs at N > 1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -324,6 +359,9 @@ def main():
     drr_kwargs = json.loads(args.drr_kwargs) if args.drr_kwargs else None
     leg = render_leg(dev, subject, args.renderer, not args.no_voxel_grad, rot, xyz, H, delx, args.n_points, args.steps, args.warmup,
                      exchange=exchange, update_volume=args.update_volume, drr_kwargs=drr_kwargs)
+    if args.dump_outputs and rank == 0:   # (before anything else runs the step again)
+        dump_outputs(leg, args.dump_outputs)
+    leg.pop("img")
     elapsed = leg["elapsed"]
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -366,7 +404,7 @@ def main():
                     "bucketed async all_reduce (SUM) of density.grad over slabs of the first axis, issued after the backward, waited for "
                     "at the end of the step; not overlapped with the splat"),
         }
-        if vg:   # the same step without it, a short loop behind the timed region (same barrier discipline)
+        if vg and args.full:   # the same step without it, a short loop behind the timed region (same barrier discipline)
             exchange.volume_grad = False
             leg["step"]()
             torch.cuda.synchronize()
@@ -441,8 +479,8 @@ def main():
     # step through the Siddon renderer; (iii) the pose-only backward -- the only backward xvr itself requests
     # (registrar/base.py:252, trainer.py:223); (iv) the knob sets SURVEY Appendix A recalls; (v) C4 = one registration iteration
     # at 256^2 and 512^2; (vi) C5 = the render side of one training step, also under the per-ray clip.  The LINE carries their
-    # scalars; the kernel tables go to bench_full.json.
-    if world == 1 and not args.no_variants and args.renderer == "trilinear" and not args.no_voxel_grad and not use_dist and not drr_kwargs:
+    # scalars; the kernel tables go to bench_full.json.  Only with --full.
+    if args.full and world == 1 and not args.no_variants and args.renderer == "trilinear" and not args.no_voxel_grad and not use_dist and not drr_kwargs:
         step = leg["step"]
 
         def timed_loop(n, **kws):
@@ -506,7 +544,7 @@ def main():
         result["ms_per_step_volume_changing"] = variants["ms_per_step_volume_changing"]
         result["clip_to_volume_ms_per_step"] = variants["clip_to_volume_ms_per_step"]
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(vol, leg["drr"], leg["rot"], leg["xyz"], leg["spec"], args)
     if use_dist:   # (before the line: whatever the backend says while it shuts down must not follow it on stdout)
         dist.barrier()

@@ -36,7 +36,7 @@ def _scalars_only(d, depth=0):
 def test_bench_json_contract(renderer, tmp_path):
     full_path = tmp_path / "full.json"
     cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--size", "64", "--det", "32",
-           "--batch", "4", "--n-points", "80", "--renderer", renderer, "--cpu-rays", "256", "--c5", "--full-json", str(full_path)]
+           "--batch", "4", "--n-points", "80", "--renderer", renderer, "--cpu-rays", "256", "--c5", "--full", "--full-json", str(full_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _the_line(out.stdout)
@@ -102,6 +102,63 @@ def test_bench_json_contract(renderer, tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is the headline alone: no secondary legs, no CPU baseline; every kernel of the step launched exactly
+    --steps times in the timed region.  --dump-outputs writes the last timed step's DRRs and gradients in float32, below 64 MB, and a
+    second run with the same arguments (the same seeded inputs) writes the same numbers."""
+    import numpy as np
+
+    common = ["--steps", "3", "--warmup", "1", "--size", "64", "--det", "32", "--batch", "4", "--n-points", "80"]
+    dumps = []
+    for run in range(2):
+        full_path, dump = tmp_path / f"full{run}.json", tmp_path / f"out{run}"
+        out = subprocess.run([sys.executable, str(ROOT / "bench.py"), *common, "--full-json", str(full_path), "--dump-outputs", str(dump)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = _the_line(out.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "kernels_ms"):
+            assert key in d, key
+        assert not {"cpu_baseline", "variants", "value_clip_per_ray", "value_clip_batch", "value_volume_changing"} & set(d), sorted(d)
+        assert d["steps"] == 3 and abs(d["value"] - 4 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+        full = json.loads(full_path.read_text())
+        assert "variants" not in full and "cpu_baseline" not in full
+        assert full["kernels"] and all(k["launches"] == 3 for k in full["kernels"].values()), full["kernels"]
+        files = {p.name: np.load(p) for p in dump.glob("*.npy")}
+        assert set(files) == {"drr.npy", "grad_rot.npy", "grad_xyz.npy", "grad_density.npy"}, sorted(files)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+        assert files["drr.npy"].shape == (4, 1, 32, 32) and files["grad_rot.npy"].shape == files["grad_xyz.npy"].shape == (4, 3)
+        assert files["grad_density.npy"].shape == (64, 64, 64) and np.abs(files["grad_density.npy"]).max() > 0
+        assert files["drr.npy"].max() > 0 and sum(p.stat().st_size for p in dump.glob("*.npy")) < 64e6
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][name], a, rtol=1e-5, atol=1e-6 * np.abs(a).max(), err_msg=name)
+
+
+def test_bench_dump_samples_a_large_output_at_fixed_indices(tmp_path):
+    """No GPU needed: an array above its cap is written as a seeded sample whose indices depend on the array's size alone."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    n = bench.DUMP_CAPS["grad_density"] + 1000
+    density = torch.arange(n, dtype=torch.float32).requires_grad_(True)
+    density.grad = density.detach() * 2
+    rot = torch.zeros(2, 3, requires_grad=True)
+    rot.grad = torch.ones(2, 3)
+    leg = {"img": torch.ones(2, 1, 4, 4), "rot": rot, "xyz": torch.zeros(2, 3, requires_grad=True), "density": density}
+    for run in range(2):
+        bench.dump_outputs(leg, tmp_path / str(run))
+    names = sorted(p.name for p in (tmp_path / "0").iterdir())
+    assert names == ["drr.npy", "grad_density_sample.npy", "grad_rot.npy"]       # (no d/dxyz: its .grad is None)
+    s0, s1 = (np.load(tmp_path / str(r) / "grad_density_sample.npy") for r in range(2))
+    assert s0.dtype == np.float32 and s0.shape == (bench.DUMP_CAPS["grad_density"],) and np.array_equal(s0, s1)
+    assert (np.diff(s0) >= 0).all() and s0.max() > 2 * (n - 2000) and s0.min() < 2000   # sorted indices, spread over the array
+    assert sum(bench.DUMP_CAPS.values()) * 4 <= 64e6
+
+
+@pytest.mark.gpu
 def test_bench_one_rank_over_rccl():
     """--force-dist --backend nccl: the process group is RCCL and the step's all_gather_into_tensor runs on it -- on ONE rank, so
     that the first RCCL call of this project does not happen on the driver's 8-GPU node (missing 4)."""
@@ -152,7 +209,7 @@ def test_bench_bare_command_launches_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     common = ["--steps", "2", "--warmup", "1", "--size", "64", "--det", "32", "--n-points", "80", "--batch", "4"]
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--single-device", "--backend", "gloo", "--check-gather",
-                          "--full-json", str(tmp_path / "n2.json"), *common], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--full", "--full-json", str(tmp_path / "n2.json"), *common], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _the_line(out.stdout)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 8 and d["gather_check"]["equal"] is True
@@ -174,7 +231,7 @@ def test_bench_bare_command_launches_its_own_ranks(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("slabs", [4, 1], ids=["overlapped slabs", "buckets after the backward"])
 def test_bench_two_ranks_weak_scaling_contract(slabs):
-    d = _torchrun_bench(["--batch", "4", "--check-gather", "--check-volume-grad", "--volume-grad-slabs", str(slabs)], 29611 + slabs)
+    d = _torchrun_bench(["--batch", "4", "--check-gather", "--check-volume-grad", "--volume-grad-slabs", str(slabs), "--full"], 29611 + slabs)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["global_batch"] == 8
     # the step's second exchange: the voxel gradients of the two ranks, summed inside the timed step (slab by slab
     # while the backward runs, or by bucketed async all-reduces behind it) -- equal to the gradient of the union batch rendered by one process through the HIP path --

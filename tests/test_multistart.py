@@ -40,6 +40,7 @@ def test_training_step_one_volume_per_rank_two_ranks():
     assert out.returncode == 0, out.stderr[-3000:]
     # (two processes write to one pipe: a report can land behind another line's text instead of on a line of its own)
     import re
-    reports = re.findall(r"rank \d/2: [^\n]*", out.stdout)
+    # (so a report ends where the next one starts, or at the end of its line)
+    reports = re.findall(r"rank \d/2: .*?(?=rank \d/2: |\n|$)", out.stdout)
     assert len(reports) == 2, out.stdout
     assert all("weights identical across ranks: True" in l and "every 4 steps" in l for l in reports)
