@@ -138,6 +138,50 @@ int xvr_sim_transform_backward(const float* x, const float* grad_y, int B, long 
  */
 int xvr_sim_dice_bool(const unsigned char* pred, const unsigned char* truth, int B, int C, int n, float* dice, void* stream);
 
+/*
+ * The training step's on-device X-ray augmentations (xvr's XrayAugmentations: Standardize -> CLAHE -> gamma -> box blur ->
+ * Gaussian noise -> sharpness -> erasing -> border crop, each random op applied per image; DESIGN.md "Augmentations").
+ * Forward only.  The caller standardises the batch first (xvr_sim_transform_forward, per_image = 0, mean 0, std 1) and
+ * passes that image `s` [B][H][W] to both passes:
+ *
+ *   xvr_sim_augment_clahe_lut   one workgroup per (image, tile) of the images whose CLAHE flag is set: the 8 x 8 tiles' clipped
+ *                               and equalised 256-entry LUTs, lut [B][8][8][256] bytes (xvr_sim_augment_lut_bytes(B); the
+ *                               rows of the other images are not written).  clip_per_image = 0: every selected image uses the
+ *                               clip limit of the FIRST selected image, 1: its own.
+ *   xvr_sim_augment_chain       out [B][H][W]: every op of the chain in one pass (reads `lut` only for images with CLAHE set).
+ *                               Gaussian noise is z(seed, image, y, x) * noise_std from a Philox-4x32-10 + Box-Muller generator
+ *                               keyed on the image's seed columns (restated on the host: tests/augment_restated.py).
+ *
+ * `params` [B][XVR_SIM_AUG_COLS] float32, the columns below (flags are 0 / 1; the rectangle, crop and seed columns hold
+ * integers; seeds < 2^24).  Images need H, W >= 2 and the CLAHE tiles' reflect padding smaller than the image
+ * (8 * tile - H < H with tile = ceil(H / 8) rounded up to even; the same for W).
+ */
+#define XVR_SIM_AUG_CLAHE 0      /* flag                                        */
+#define XVR_SIM_AUG_CLIP 1       /* CLAHE clip limit (<= 0: no clipping)        */
+#define XVR_SIM_AUG_GAMMA_ON 2   /* flag                                        */
+#define XVR_SIM_AUG_GAMMA 3      /* gamma                                       */
+#define XVR_SIM_AUG_BLUR 4       /* flag: 3 x 3 box blur, reflect borders       */
+#define XVR_SIM_AUG_NOISE 5      /* flag                                        */
+#define XVR_SIM_AUG_SHARP_ON 6   /* flag                                        */
+#define XVR_SIM_AUG_SHARP 7      /* sharpness factor                            */
+#define XVR_SIM_AUG_ERASE 8      /* flag                                        */
+#define XVR_SIM_AUG_ERASE_Y 9    /* erased rectangle: top row, left column, height, width */
+#define XVR_SIM_AUG_ERASE_X 10
+#define XVR_SIM_AUG_ERASE_H 11
+#define XVR_SIM_AUG_ERASE_W 12
+#define XVR_SIM_AUG_CROP_ON 13   /* flag                                        */
+#define XVR_SIM_AUG_CROP 14      /* pixels within this distance of the border are zeroed */
+#define XVR_SIM_AUG_SEED_LO 15   /* Philox key words of the image's noise       */
+#define XVR_SIM_AUG_SEED_HI 16
+#define XVR_SIM_AUG_COLS 17
+
+int xvr_sim_augment_param_cols(void);
+size_t xvr_sim_augment_lut_bytes(int B);
+int xvr_sim_augment_clahe_lut(const float* s, const float* params, int B, int H, int W, int clip_per_image, unsigned char* lut,
+                              void* stream);
+int xvr_sim_augment_chain(const float* s, const float* params, const unsigned char* lut, int B, int H, int W, float noise_std,
+                          float erase_value, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

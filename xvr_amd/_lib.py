@@ -11,7 +11,7 @@ import warnings
 
 from .build import LIB, HipccMissing, build_library, is_stale
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 JAC_STRIDE = 8
 ALPHA_WINDOW_FLOATS = 16   # XVR_DRR_ALPHA_WINDOW_FLOATS
 
@@ -117,6 +117,10 @@ EXPORTS = {
     "xvr_sim_transform_backward": ([_P, _P, _I, ctypes.c_longlong, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P], ctypes.c_int),
     "xvr_sim_dice_bool": ([_P, _P, _I, _I, _I, _P, _P], ctypes.c_int),
     "xvr_sim_gaussian_blur5": ([_P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P], ctypes.c_int),
+    "xvr_sim_augment_param_cols": ([], ctypes.c_int),
+    "xvr_sim_augment_lut_bytes": ([_I], ctypes.c_size_t),
+    "xvr_sim_augment_clahe_lut": ([_P, _P, _I, _I, _I, _I, _P, _P], ctypes.c_int),
+    "xvr_sim_augment_chain": ([_P, _P, _P, _I, _I, _I, ctypes.c_float, ctypes.c_float, _P, _P], ctypes.c_int),
     "xvr_drr_hu_stats": ([_P, ctypes.c_longlong, _P, _P], ctypes.c_int),
     "xvr_drr_hu_to_density": ([_P, ctypes.c_longlong, _P, ctypes.c_float, _P, _P], ctypes.c_int),
     "xvr_drr_rays_forward": ([_P, _I, _I, _I, _P, _P, _P, _P], ctypes.c_int),
