@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define XVR_DRR_ABI_VERSION 11   /* 11: xvr_sim_augment_* (the training step's X-ray augmentations); 10: xvr_sim_ncc_registration_step (the tail of a registration iteration in the similarity's launches); 9: xvr_drr_pack_hu_labels_ytiles, options siddon_splat / gather_splat = 3 / siddon_slab = 2, pose kind 6 (rotation_10d), non-exact Siddon index maps on the slab march and the brick splat, guard-banded fixed point; 8: volume_layout 3 + xvr_drr_pack_ytiles / _labels_ytiles (tiled y-pair copy), xvr_pose_camera_forward_param / xvr_pose_opt_step_param (device-resident registration for every parameterisation; xvr_pose_opt_state holds 13 parameters), xvr_sim_equalize_* write / take the normalised output, options tile_geom, siddon_slab, siddon_gather_fast; 7: xvr_drr_foreground, xvr_drr_pack_labels_ypairs, xvr_sim_dice_bool, xvr_sim_transform_* (xvr_sim.h), xvr_pose_convert_* (xvr_pose.h); 6: xvr_drr_spec.alpha_window + xvr_drr_alpha_window (clip_to_volume = 2); 5: xvr_drr_set_option / xvr_drr_get_option (the A/B switches are no longer getenv calls per launch); 4: volume_layout 2 + xvr_drr_pack_bricks (siddon forward); 3: xvr_drr_spec.volume_layout + xvr_drr_pack_ypairs; 2: xvr_sim_spec grew, camera-driven forwards, packed labels, xvr_pose.h */
+#define XVR_DRR_ABI_VERSION 12   /* 12: xvr_drr_trilinear_backward / xvr_drr_siddon_backward take slab_index, slab_count (an argument of the call where a process-wide option used to carry it); 11: xvr_sim_augment_* (the training step's X-ray augmentations); 10: xvr_sim_ncc_registration_step (the tail of a registration iteration in the similarity's launches); 9: xvr_drr_pack_hu_labels_ytiles, options siddon_splat / gather_splat = 3 / siddon_slab = 2, pose kind 6 (rotation_10d), non-exact Siddon index maps on the slab march and the brick splat, guard-banded fixed point; 8: volume_layout 3 + xvr_drr_pack_ytiles / _labels_ytiles (tiled y-pair copy), xvr_pose_camera_forward_param / xvr_pose_opt_step_param (device-resident registration for every parameterisation; xvr_pose_opt_state holds 13 parameters), xvr_sim_equalize_* write / take the normalised output, options tile_geom, siddon_slab, siddon_gather_fast; 7: xvr_drr_foreground, xvr_drr_pack_labels_ypairs, xvr_sim_dice_bool, xvr_sim_transform_* (xvr_sim.h), xvr_pose_convert_* (xvr_pose.h); 6: xvr_drr_spec.alpha_window + xvr_drr_alpha_window (clip_to_volume = 2); 5: xvr_drr_set_option / xvr_drr_get_option (the A/B switches are no longer getenv calls per launch); 4: volume_layout 2 + xvr_drr_pack_bricks (siddon forward); 3: xvr_drr_spec.volume_layout + xvr_drr_pack_ypairs; 2: xvr_sim_spec grew, camera-driven forwards, packed labels, xvr_pose.h */
 
 #define XVR_DRR_OK 0
 #define XVR_DRR_E_ARG (-1)     /* bad argument (null pointer, non-positive size, unsupported combo) */
@@ -108,12 +108,6 @@ const char* xvr_drr_last_error(void);
  *                              viewing axis per workgroup, candidates from an LDS copy of the brick's footprint, planes in
  *                              crossing order | the window of the eight projected corners, one brick per workgroup,
  *                              candidates from global memory (A/B: equal to rounding)                           [1]
- *   "gather_slab"   0 | index + 256 * count   the voxel gradient of xvr_drr_*_backward in `count` slabs of whole 16^3-brick planes
- *                              along x, ONE backward call per slab: index 0 first, same arguments and workspace.  Call i adds the
- *                              gradient of the voxels x in [16 * (i * nb / count), 16 * ((i + 1) * nb / count)), nb = ceil(D0 / 16);
- *                              pose gradients, and renders the brick splats do not serve (the whole volume), come with call 0.
- *                              A caller can hand slab i to a collective while slab i + 1 is computed (xvr_amd.distributed
- *                              .SlabAllReduce).  The caller resets the option to 0 afterwards.                      [0]
  * Returns XVR_DRR_E_ARG for an unknown name or a value outside the option's range.
  */
 int xvr_drr_set_option(const char* name, int value);
@@ -202,12 +196,20 @@ int xvr_drr_trilinear_forward(const float* volume, const float* mask, int D0, in
  *                A non-finite grad_out turns the voxels of the 16^3 bricks its pose touches into NaN.  Otherwise -- or when the kernel finds on the
  *                device that the targets are not a lattice -- it falls back to a scatter with fp32 atomics: same result
  *                up to summation order, more than an order of magnitude slower on MI355X.
+ *   slab_index, slab_count   (this function and xvr_drr_siddon_backward) slab_count <= 1: the whole voxel gradient in this call.
+ *                Otherwise the voxel gradient in slab_count slabs of whole 16^3-brick planes along x, ONE backward call per slab:
+ *                slab_index 0 first, same arguments and workspace.  Call i adds the gradient of the voxels x in
+ *                [16 * (i * nb / slab_count), 16 * ((i + 1) * nb / slab_count)), nb = ceil(D0 / 16); pose gradients, and renders
+ *                the brick splats do not serve (the whole volume), come with call 0.  A caller can hand slab i to a collective
+ *                while slab i + 1 is computed (xvr_amd.distributed.SlabAllReduce).  slab_index outside [0, slab_count) is
+ *                XVR_DRR_E_ARG.
  */
 int xvr_drr_trilinear_backward(const float* volume, const float* mask, int D0, int D1, int D2, int C,
                                const float* source, const float* target, const float* raylen,
                                int B, int n, const xvr_drr_spec* spec, const float* grad_out,
                                float* grad_volume, float* grad_source, float* grad_target,
-                               float* grad_raylen, void* workspace, size_t workspace_bytes, void* stream);
+                               float* grad_raylen, void* workspace, size_t workspace_bytes, void* stream,
+                               int slab_index, int slab_count);
 
 /* Siddon exact ray tracing, same contract.  Replaces Siddon.forward(volume, source, target, img, mask=...).
  *   work counts voxel segments traversed. */
@@ -220,7 +222,8 @@ int xvr_drr_siddon_backward(const float* volume, const float* mask, int D0, int 
                             const float* source, const float* target, const float* raylen,
                             int B, int n, const xvr_drr_spec* spec, const float* grad_out,
                             float* grad_volume, float* grad_source, float* grad_target,
-                            float* grad_raylen, void* workspace, size_t workspace_bytes, void* stream);
+                            float* grad_raylen, void* workspace, size_t workspace_bytes, void* stream,
+                            int slab_index, int slab_count);
 
 /*
  * Pose-side backward from the jacobian saved by a forward call: an elementwise product with the

@@ -20,8 +20,8 @@ def test_module_exports_and_abi():
 
     for name in ("AugmentSpec", "XrayAugmentations", "sample_params", "apply", "clahe_luts", "standardize", "COLS", "FLAGS"):
         assert hasattr(augment, name), name
-    assert _lib.ABI_VERSION == 11
-    assert re.search(r"#define XVR_DRR_ABI_VERSION 11\b", (ROOT / "include" / "xvr_drr.h").read_text())
+    assert _lib.ABI_VERSION == 12
+    assert re.search(r"#define XVR_DRR_ABI_VERSION 12\b", (ROOT / "include" / "xvr_drr.h").read_text())
     header = (ROOT / "include" / "xvr_sim.h").read_text()
     cols = {m[0]: int(m[1]) for m in re.findall(r"#define XVR_SIM_AUG_([A-Z_]+) (\d+)", header)}
     for name, col in cols.items():

@@ -1,7 +1,7 @@
-"""The voxel gradient in x slabs (option gather_slab of the library, xvr_amd.renderers.VOXEL_GRAD_SLABS): one launch per slab of whole
+"""The voxel gradient in x slabs (slab_index / slab_count of xvr_drr_*_backward, xvr_amd.renderers.VOXEL_GRAD_SLABS): one launch per slab of whole
 16^3-brick planes so that a caller can start exchanging slab i while slab i + 1 is computed (bench.py at N > 1).  Whatever kernel
 serves the render, the slabbed backward must leave the SAME bits as the single launch, call the hook once per slab with that slab's
-view of the gradient, in order, and leave the option cleared."""
+view of the gradient, in order, and leave nothing behind in the library: the slab is an argument of the call, not an option."""
 import pytest
 import torch
 
@@ -32,7 +32,7 @@ def _backward(case, spec, slabs, w, grid_w):
     finally:
         renderers.VOXEL_GRAD_SLABS = None
     torch.cuda.synchronize()
-    assert _lib.get_option("gather_slab") == 0
+    assert _lib.load().xvr_drr_set_option(b"gather_slab", 1) == -1   # XVR_DRR_E_ARG: no such option, nothing left to leak
     return vol.grad, src.grad, seen
 
 
@@ -57,3 +57,20 @@ def test_slabbed_voxel_gradient_is_the_single_launch_bit_for_bit(renderer, kw, w
     assert sum(n for _, n, _ in seen) == shape[0]
     rows = [p for _, _, p in seen]
     assert rows == sorted(rows) and rows[0] == gk.data_ptr(), "views of the gradient autograd hands out, first slab first"
+
+
+def test_plain_backward_after_a_slabbed_one_is_the_single_launch_bit_for_bit():
+    """A slabbed backward leaves no state in the process: the plain backward that follows it computes the whole gradient
+    (the brick splat, whose slabbed calls each take a share of the bricks)."""
+    from xvr_amd.spec import RenderSpec
+
+    shape, hw = (52, 37, 45), (40, 44)
+    renderer, kw, why = CASES[0]
+    spec = RenderSpec(renderer=renderer, **kw)
+    case = make_case(seed=23, shape=shape, height=hw[0], width=hw[1], delx=0.9 * max(shape) / max(hw))
+    w = torch.randn(2, 1, hw[0] * hw[1], generator=torch.Generator().manual_seed(3))
+    g_ref, _, _ = _backward(case, spec, 0, w, hw[1])
+    _backward(case, spec, 3, w, hw[1])
+    g_after, _, seen = _backward(case, spec, 0, w, hw[1])
+    assert seen == [] and g_ref.abs().max() > 0
+    assert torch.equal(g_ref, g_after), why

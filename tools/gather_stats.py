@@ -28,6 +28,8 @@ drr = DRR(read(vol, orientation="AP"), 1020.0, 256, 1.08821875, renderer="siddon
 pose = get_random_pose(135.0, 225.0, -45.0, 45.0, -15.0, 15.0, -150.0, 150.0, 450.0, 1000.0, -150.0, 150.0, 116,
                        generator=torch.Generator().manual_seed(0)).to(dev)
 density = drr.density.clone().requires_grad_()
+if not SIDDON:
+    _lib.set_option("gather_splat", 0)   # the fp32 table gather, which holds the counters (the default is the brick splat)
 raw = ctypes.CDLL(str(_lib.library_path()))
 out = (ctypes.c_ulonglong * 8)()
 drr(pose, density=density).sum().backward()          # warm-up

@@ -11,7 +11,7 @@ import warnings
 
 from .build import LIB, HipccMissing, build_library, is_stale
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 JAC_STRIDE = 8
 ALPHA_WINDOW_FLOATS = 16   # XVR_DRR_ALPHA_WINDOW_FLOATS
 
@@ -86,7 +86,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _AX = ctypes.POINTER(ctypes.c_int)
 _FWD = [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, ctypes.POINTER(CSpec), _P, _P, _P, _P]
-_BWD = [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, ctypes.POINTER(CSpec), _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]
+_BWD = [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, ctypes.POINTER(CSpec), _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _I, _I]
 
 EXPORTS = {
     "xvr_drr_abi_version": ([], ctypes.c_int),

@@ -51,7 +51,7 @@ def diagnostic_path(name: str) -> Path:
 
 def build_diagnostic_library(define, out: Path, only=None) -> Path:
     """A separate library with extra -D's (e.g. XVR_GATHER_STATS; a string or a list of them) for the measuring tools
-    under tools/; never loaded by the package itself and never written into xvr_amd/lib/ (some of these builds compute
+    under tools/; never loaded by the package itself and never written into xvr_amd/lib/ (such a build may compute
     deliberately wrong sums).  ``only``: the translation units the defines touch (file names) -- the others are taken from
     the product build's objects, which must be up to date (build_library())."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

@@ -5,11 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "xvr_drr.h"
-
-namespace xvr_detail {
-int option(int id);
-}
+#include "drr_common.hiph"   // (xvr_detail::Option, xvr_detail::option)
 
 namespace {
 thread_local char g_err[512] = "";
@@ -33,7 +29,6 @@ const OptionDef OPTIONS[] = {
     {"siddon_slab", "XVR_DRR_SIDDON_SLAB", 1, 0, 2},
     {"siddon_gather_fast", "XVR_DRR_SIDDON_GATHER_FAST", 1, 0, 1},
     {"siddon_splat", "XVR_DRR_SIDDON_SPLAT", 1, 0, 2},
-    {"gather_slab", "XVR_DRR_GATHER_SLAB", 0, 0, 0xffff},
 };
 constexpr int N_OPTIONS = sizeof(OPTIONS) / sizeof(OPTIONS[0]);
 std::atomic<int> g_opt[N_OPTIONS];
@@ -45,7 +40,7 @@ struct OptionInit {
             const char* e = getenv(OPTIONS[i].env);
             if (e && *e) {
                 int gx = 0, gy = 0;
-                if (i == 3 && sscanf(e, "%dx%d", &gx, &gy) == 2) v = (gx & 0xff) | (gy << 8);   // "<gx>x<gy>" tiles
+                if (i == xvr_detail::OPT_ORDER_GROUP && sscanf(e, "%dx%d", &gx, &gy) == 2) v = (gx & 0xff) | (gy << 8);   // "<gx>x<gy>" tiles
                 else v = atoi(e);
                 if (v < OPTIONS[i].lo || v > OPTIONS[i].hi) v = OPTIONS[i].def;
             }

@@ -380,7 +380,7 @@ __device__ __forceinline__ float linspace_sel(int k, int N, float near_, float f
 // take over from there once phase B is done.
 // Where the time goes (C2): the kernel is VALU-issue bound -- 8.4e9 wave-instructions of which the packed ones cost two
 // issues, ~80 % of the issue slots of an 11.8 ms launch (profiles/r02_trilinear_rocprof_summary.md), at 41 of 64 lanes.
-// A loads-ablated build (tools/ablate_gather.py) runs in 8.7 ms and one with half the loads in 10.6 ms, but that is NOT
+// A loads-ablated build (round 2) ran in 8.7 ms and one with half the loads in 10.6 ms, but that is NOT
 // the memory cost: with constant candidates the compiler hoists their arithmetic out of the trip.  The honest test of the
 // memory hypothesis was a variant that takes the sample positions from the lattice constants and loads only the 4-byte
 // weights (one 8-byte load per trip instead of two 16-byte ones): 13.2 ms -- slower, for its extra per-row arithmetic.
@@ -392,15 +392,9 @@ __device__ __forceinline__ float linspace_sel(int k, int N, float near_, float f
 // VALU instructions per trip instead of 47, yet 12.1-13.0 ms -- a v_pk_*_f32 costs two plain issues on gfx950, so the
 // instruction count is not the time; the compiler's own pairing of the eight accumulations is as far as packing goes).
 // ---------------------------------------------------------------------------------------------
-#ifndef XVR_TAB_ROWS   // (both overridable for the tuning builds of tools/tune_gather.py)
-#define XVR_TAB_ROWS 13
-#endif
-#ifndef XVR_TAB_WAVES
-#define XVR_TAB_WAVES 6
-#endif
 // 13 x 64 lanes x 8 B = 6.5 KiB of LDS per wavefront: 24 wavefronts per CU (6 per SIMD) fit in 160 KiB; measured flat from
 // (7 per SIMD, 11 rows) to (6, 13) and (5, 15), 5-8 % worse at (8, 9) and (4, 19)
-constexpr int TAB_ROWS = XVR_TAB_ROWS;
+constexpr int TAB_ROWS = 13, TAB_WAVES = 6;
 constexpr unsigned TAB_R0_BITS = 24, TAB_N_BITS = 8;   // entry.x = first element of the run in q | count << 24; entry.y = alpha_k
 constexpr unsigned TAB_MAX_RAYS = 1u << TAB_R0_BITS;
 
@@ -427,26 +421,18 @@ __device__ __forceinline__ void gather_pair(const float4 ta, const float4 tb, co
     }
 }
 
-#if defined(XVR_GATHER_ABLATE) && XVR_GATHER_ABLATE == 2   // diagnostic build: half the loads (the pair's second = its first)
-#define XVR_LOAD_Q(ptr, k) ((ptr)[0])
-#elif defined(XVR_GATHER_ABLATE)   // diagnostic build only (tools/ablate_gather.py): same arithmetic, no memory traffic
-#define XVR_LOAD_Q(ptr, k) make_float4((float)(k) * 0.25f, 0.5f, 0.75f, 1.f)
-#else
-#define XVR_LOAD_Q(ptr, k) ((ptr)[k])
-#endif
-
 __device__ __forceinline__ void gather_row(const float4* __restrict__ row, const int n, const float Ax, const float Ay, const float Az,
                                            const float Bx, const float By, const float Bz, float (&acc)[8]) {
     for (int j = 0; j < n; j += 2) {
         const bool two = j + 1 < n;
-        const float4 ta = XVR_LOAD_Q(row, j);
-        float4 tb = XVR_LOAD_Q(row, two ? j + 1 : j);
+        const float4 ta = row[j];
+        float4 tb = row[two ? j + 1 : j];
         tb.w = two ? tb.w : 0.f;
         gather_pair(ta, tb, Ax, Ay, Az, Bx, By, Bz, acc);
     }
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(XVR_TAB_WAVES, XVR_TAB_WAVES))) void k_trilinear_gather_tab(GatherArgs G) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TAB_WAVES, TAB_WAVES))) void k_trilinear_gather_tab(GatherArgs G) {
     if (*G.flag > __float_as_uint(GATHER_DEV_TOL)) return;  // not a lattice: the scatter kernel runs instead
     if (G.only_if_fine >= 0 && (int)(G.flag[3] != 0u) != G.only_if_fine) return;   // (the splat took the launch)
     __shared__ uint2 tab[TAB_ROWS * 64];
@@ -588,7 +574,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(XVR_TAB_WAVE
                 bool live = next_row();
                 while (live) {
                     XVR_STAT_WAVE(6);
-                    const float4 ta = XVR_LOAD_Q(ptr, 0), tb = XVR_LOAD_Q(ptr, 1);
+                    const float4 ta = ptr[0], tb = ptr[1];
                     gather_pair(ta, tb, al, al, al, Bx, By, Bz, acc);
                     ptr += 2;
                     rem -= 2;
@@ -1018,20 +1004,13 @@ __device__ __forceinline__ float min_raw(float a, float b) { float r; asm("v_min
 //     one-projection bound, a few coalesced loads -- into its slice of LDS and the lanes read their candidates with
 //     ds_read_b128.  Footprints beyond the slice (SG_FOOT pixels), bricks that reach the source plane and poses with cut rays
 //     take the global loads as before.
-#ifndef XVR_SG_CUM     // 1: sign-sorted visits accumulate 3-D prefix sums of the eight sums (see the candidate)
-#define XVR_SG_CUM 1
-#endif
-#ifndef XVR_SG_FOOT
-#define XVR_SG_FOOT 480
-#endif
-#ifndef XVR_SG_WAVES   // wavefronts per SIMD the LDS slices leave room for: 160 KB / (4 x 16 B x SG_FOOT) workgroups of four.  Measured at
-                       // C3 (ms, launch incl. prep / cull): 640 px x 4 -> 8.20, 512 x 5 (only four fit) 8.24, 416-496 x 5 -> 7.63, 400 x 6 -> 8.38
-                       // (spills), 320 x 7 -> 8.88, 256 x 8 -> 12.2, 960-1280 x 2 -> 12.9: occupancy matters more than the last footprints
-#define XVR_SG_WAVES 5
-#endif
-constexpr int SG_FOOT = XVR_SG_FOOT;
+// Sign-sorted visits accumulate 3-D prefix sums of the eight sums (see the candidate).
+// SG_WAVES: wavefronts per SIMD the LDS slices leave room for: 160 KB / (4 x 16 B x SG_FOOT) workgroups of four.  Measured at
+// C3 (ms, launch incl. prep / cull): 640 px x 4 -> 8.20, 512 x 5 (only four fit) 8.24, 416-496 x 5 -> 7.63, 400 x 6 -> 8.38
+// (spills), 320 x 7 -> 8.88, 256 x 8 -> 12.2, 960-1280 x 2 -> 12.9: occupancy matters more than the last footprints
+constexpr int SG_FOOT = 480, SG_WAVES = 5;
 template <bool FAST>
-__global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu(FAST ? XVR_SG_WAVES : 6, FAST ? XVR_SG_WAVES : 6))) void k_siddon_gather_vol2(GatherArgs G) {
+__global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu(FAST ? SG_WAVES : 6, FAST ? SG_WAVES : 6))) void k_siddon_gather_vol2(GatherArgs G) {
     if (*G.flag > __float_as_uint(GATHER_DEV_TOL)) return;
     __shared__ float4 s_foot[FAST ? 4 : 1][FAST ? SG_FOOT : 1];
     int bx, by, bz;
@@ -1222,7 +1201,6 @@ __global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu
                 }
                 const float yl[2] = {SORTED ? y0 : min_raw(y0, y1), SORTED ? y1 : min_raw(y1, y2)}, yh[2] = {SORTED ? y1 : max_raw(y0, y1), SORTED ? y2 : max_raw(y1, y2)};
                 const float zl[2] = {SORTED ? z0 : min_raw(z0, z1), SORTED ? z1 : min_raw(z1, z2)}, zh[2] = {SORTED ? z1 : max_raw(z0, z1), SORTED ? z2 : max_raw(z1, z2)};
-#if XVR_SG_CUM
                 if (SORTED) {
                     // planes in crossing order: the ray is inside {x < x_i, y < y_j, z < z_k} from its entry into the block to the first
                     // of the three planes -- nested prefixes of one ray.  Their lengths are the 3-D PREFIX SUMS of the eight chords, so the
@@ -1236,7 +1214,6 @@ __global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu
                     }
                     return;
                 }
-#endif
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int a = e >> 2, b = (e >> 1) & 1, c = e & 1;
@@ -1245,10 +1222,6 @@ __global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu
                     acc[e] = fmaf(__builtin_amdgcn_fmed3f(ex - en, 0.f, 1.f), t.w, acc[e]);
                 }
             };
-#if defined(XVR_SG_ABLATE) && XVR_SG_ABLATE == 3   // diagnostic build only: the visits without their candidates -- WRONG sums
-            acc[0] += (float)(ihi - ilo) + (float)(jhi - jlo);
-            ihi = ilo - 1;
-#endif
             XVR_STAT(0, (ihi >= ilo && jhi >= jlo) ? 1 : 0);
             XVR_STAT(4, (ihi >= ilo && jhi >= jlo) ? (ihi - ilo + 1) * (jhi - jlo + 1) : 0);
             XVR_STAT_WAVE(7);
@@ -1263,16 +1236,7 @@ __global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu
                         XVR_STAT_WAVE(6);
                         const int j1 = j < jhi ? j + 1 : j;
                         float4 ta, tb;
-#if defined(XVR_SG_ABLATE) && XVR_SG_ABLATE == 1   // diagnostic build only (tools/ablate_siddon_gather.py): no candidate loads -- WRONG sums
-                        ta = make_float4(__int_as_float(0x3a000000 + j), __int_as_float(0x3a800000 + i), __int_as_float(0x3a400000 + j + i), 1.f);
-                        tb = make_float4(__int_as_float(0x3a000000 + j1), __int_as_float(0x3a800000 + i), __int_as_float(0x3a400000 + j1 + i), 1.f);
-#else
                         if (decltype(from_lds)::value) { ta = frow[j]; tb = frow[j1]; } else { ta = row[j]; tb = row[j1]; }
-#endif
-#if defined(XVR_SG_ABLATE) && XVR_SG_ABLATE == 2   // diagnostic build only: the loads without the candidates' arithmetic -- WRONG sums
-                        acc[0] += ta.x + tb.x; acc[1] += ta.y + tb.y; acc[2] += ta.z + tb.z; acc[3] += ta.w + tb.w;
-                        continue;
-#endif
                         if (j1 == j) tb.w = 0.f;
                         candidate(ta, cut, sorted);
                         candidate(tb, cut, sorted);
@@ -1304,15 +1268,11 @@ __global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu
             if (FAST && __builtin_amdgcn_ballot_w64(!same_way) == 0ull) { XVR_STAT_WAVE(3); }
 #endif
             if (FAST && __builtin_amdgcn_ballot_w64(!same_way) == 0ull) {
-#if XVR_SG_CUM
                 if (__builtin_amdgcn_ballot_w64(cur != mask) != 0ull) {   // (uniform) some lane turns its block around
                     if (cum) to_chords();
                     permute(cur ^ mask);
                 }
                 if (!cum) to_cum();
-#else
-                permute(cur ^ mask);
-#endif
                 cur = mask;
                 if (mask & 4u) { const float t_ = lx[0]; lx[0] = lx[2]; lx[2] = t_; }
                 if (mask & 2u) { const float t_ = ly[0]; ly[0] = ly[2]; ly[2] = t_; }
@@ -1356,7 +1316,8 @@ __global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu
 // (with skip_unless_flag_gt = the returned flag) right behind it.
 int xvr_detail::launch_gather(bool siddon, const float* source, const float* target, const float* raylen, const float* grad_out,
                   int B, int n, int gw, int D0, int D1, int D2, const xvr_drr_spec* sp, float* grad_volume,
-                  void* workspace, void* stream, unsigned** flag_out, const float* mask, int C, const int* siddon_olo, int siddon_splat) {
+                  void* workspace, void* stream, unsigned** flag_out, int slab_index, int slab_count, const float* mask, int C,
+                  const int* siddon_olo, int siddon_splat) {
     char* ws = static_cast<char*>(workspace);
     GatherArgs G = {};
     const bool sid_splat = siddon && siddon_splat && !mask;
@@ -1419,19 +1380,18 @@ int xvr_detail::launch_gather(bool siddon, const float* source, const float* tar
     G.words = (B + 31) / 32;
     G.gvol = grad_volume;
     *flag_out = G.flag;
-    // option gather_slab = index | count << 8: the voxel gradient in `count` x slabs of whole brick planes, one backward call per slab
+    // slab_index / slab_count (slab_count <= 1: the whole volume): the voxel gradient in `count` x slabs of whole brick planes, one backward call per slab
     // (index 0 first; same arguments and workspace), so that the caller can hand slab i to a collective while slab i + 1 is computed.
     // The brick splats take their slab's bricks; every other path does the whole volume in call 0 and nothing afterwards.
-    const int slab_opt = xvr_detail::option(xvr_detail::OPT_GATHER_SLAB), slab_K = slab_opt >> 8, slab_i = slab_opt & 0xff;
-    if (slab_K > 1 && slab_i >= slab_K) return fail(XVR_DRR_E_ARG, "gather_slab: index >= count");
-    const bool later_slab = slab_K > 1 && slab_i > 0;
+    if (slab_count > 1 && (slab_index < 0 || slab_index >= slab_count)) return fail(XVR_DRR_E_ARG, "slab_index must lie in [0, slab_count)");
+    const bool later_slab = gather_slab_later(slab_index, slab_count);
     const bool brick_splat = sid_splat || (!siddon && (psplat || (!G.clip && !G.mask && splat)));
     const int nb0 = (D0 + 15) / 16;
     G.bx0 = 0;
     G.bxn = nb0;
-    if (slab_K > 1 && brick_splat) {
-        G.bx0 = (int)((long long)slab_i * nb0 / slab_K);
-        G.bxn = (int)((long long)(slab_i + 1) * nb0 / slab_K) - G.bx0;
+    if (slab_count > 1 && brick_splat) {
+        G.bx0 = (int)((long long)slab_index * nb0 / slab_count);
+        G.bxn = (int)((long long)(slab_index + 1) * nb0 / slab_count) - G.bx0;
     }
     if (later_slab && !brick_splat) return XVR_DRR_OK;
     const long long bricks = n_bricks(D0, D1, D2, G.bd);
@@ -1460,16 +1420,6 @@ int xvr_detail::launch_gather(bool siddon, const float* source, const float* tar
         const dim3 grid((unsigned)(bricks < resident ? bricks : resident));
         if (nx) hipLaunchKernelGGL(k_siddon_splat<true>, grid, dim3(256), 0, (hipStream_t)stream, G);
         else hipLaunchKernelGGL(k_siddon_splat<false>, grid, dim3(256), 0, (hipStream_t)stream, G);
-#ifdef XVR_SS_STATS
-        {
-            hipStreamSynchronize((hipStream_t)stream);
-            unsigned long long st[8];
-            hipMemcpyFromSymbol(st, HIP_SYMBOL(g_ss_stats), sizeof(st));
-            fprintf(stderr, "ss_stats trips %llu live_lane_trips %llu walks %llu walk_lanes %llu chunks %llu cands %llu live %llu pose_visits %llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]);
-            unsigned long long z[8] = {0};
-            hipMemcpyToSymbol(HIP_SYMBOL(g_ss_stats), z, sizeof(z));
-        }
-#endif
     }
     else if (siddon && G.cells) {
         hipLaunchKernelGGL(k_siddon_gather_cells, dim3((unsigned)bricks), dim3(WG), 0, (hipStream_t)stream, G);

@@ -18,15 +18,12 @@ namespace {
 // so only the rounding of that one product differs from the unsplit walk.
 // (at most 5 wavefronts per SIMD: the walk is bound by the texture-address unit; 10.7 ms at C3 against 11.5 ms at
 //  the 8 its register count would allow and at 4)
-// XVR_SID_PIPE 1: the voxel of segment i is requested, then segment i - 1 -- whose load has had a whole step to arrive -- is
-// consumed (round 1).  0: every segment is consumed where it is loaded; the other wavefronts of the SIMD cover the latency
-// and the walk saves the hand-over of six values per step.  (tuning builds: -DXVR_SID_PIPE=...)
+// The walk is software-pipelined: the voxel of segment i is requested, then segment i - 1 -- whose load has had a whole step to
+// arrive -- is consumed (round 1).  Consuming every segment where it is loaded -- the other wavefronts of the SIMD cover the
+// latency and the walk saves the hand-over of six values per step -- lost its A/B.
 // (Round 3 also tried the trilinear forward's workgroup lockstep here -- a barrier every 1 / 4 / 16 segments for as many trips as
 // the tile's longest ray needs: 12.1 / 12.0 / 11.8 ms against 8.77.  The lanes of a Siddon wavefront are at different depths
 // after a few segments anyway, and the idle trips of the shorter rays cost more than the shared lines save.)
-#ifndef XVR_SID_PIPE
-#define XVR_SID_PIPE 1
-#endif
 template <int MODE, int MASK, bool GPOSE, bool GVOL, bool EXACT, int SPLIT = 0, bool BRICK = false>
 __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_MAX : WG) __attribute__((amdgpu_waves_per_eu(1, 5))) void k_siddon(RenderArgs A) {
     extern __shared__ float lds[];  // MASK: fwd -> channel accumulators, bwd -> upstream gradients; SPLIT: partial sums
@@ -172,16 +169,10 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_MAX : WG) __attribute__((amdgpu_
         const float lab_new = MASK == 2 ? (float)(__float_as_uint(v_new) & LABEL_MASK) : (MASK ? A.mask[off] : 0.f);
         if (inb && !first_of_slice && (!SPLIT || an > ac)) ++cnt;
         first_of_slice = false;
-#if XVR_SID_PIPE
         if (have) consume();
-#endif
         // (packed labels: the label bits are cleared from the value -- a voxel of density exactly 0 contributes exactly 0)
         p_v = inb ? (MASK == 2 ? __uint_as_float(__float_as_uint(v_new) & ~LABEL_MASK) : v_new) : 0.f; p_seg = an - ac; p_ac = ac; p_ax = ax_prev; p_off = off; p_inb = inb; p_lab = lab_new;
         have = true;
-#if !XVR_SID_PIPE
-        consume();   // (no software pipeline: see XVR_SID_PIPE)
-        have = false;
-#endif
         // advance every axis whose next plane has been reached (ties advance together), branch-free
         const bool c0 = an3[0] <= an, c1 = an3[1] <= an, c2 = an3[2] <= an;
         // A plane exactly AT a cut (routine: the cuts of opposite-face rays fall on the centre planes) is
@@ -299,9 +290,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_MAX : WG) __attribute__((amdgpu_
 // nothing extra.  Serves the unsplit one-channel forward with the exact index map on the natural layout (option siddon_slab,
 // default 1); masks, non-exact maps, the alpha-split small launches and the re-marching backward keep the merge walk.
 // =============================================================================================
-#ifndef XVR_SLAB_WAVES
-#define XVR_SLAB_WAVES 8
-#endif
+constexpr int SLAB_WAVES = 8;   // k_siddon_slab: wavefronts per SIMD at most
 __device__ __forceinline__ float sel3f(int k, float a, float b, float c) { return k == 0 ? a : (k == 1 ? b : c); }
 __device__ __forceinline__ int sel3i(int k, int a, int b, int c) { return k == 0 ? a : (k == 1 ? b : c); }
 __device__ __forceinline__ float med3f(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
@@ -322,7 +311,7 @@ __device__ __forceinline__ float med3f(float x, float lo, float hi) { return __b
 // bricks, the three LDS tables read by index instead of one slab ahead.  ~32 vector instructions per slab on top of the exact
 // march's; the merge walk it replaces for these maps spends ~90 per SEGMENT.
 template <bool JAC, bool BRICK, bool NX = false>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_SLAB_WAVES))) void k_siddon_slab(RenderArgs A) {
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, SLAB_WAVES))) void k_siddon_slab(RenderArgs A) {
     extern __shared__ unsigned slab_tab[];   // BRICK: byte offsets fx[-1 .. D0], fy[-1 .. D1], fz[-1 .. D2] (indices clamped)
     int b, r;
     const bool valid = map_ray(A, b, r, threadIdx.x);
@@ -438,11 +427,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_SLAB_
     // Loads go through a buffer resource over the volume (an offset beyond it returns 0 without a memory request: the bounds net);
     // the three loads of a slab are predicated in EXEC, see the loop.
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vol), (short)0, vol_bytes, 0x00020000);
-#if defined(XVR_SLAB_ABLATE)   // diagnostic build only (tools/ablate_siddon_slab.py): voxel values made up from the offset, no loads -- WRONG image
-    auto ld = [&](bool p, int o) { return p ? __int_as_float(0x3f000000 | (o & 0xffff)) : 0.f; };
-#else
     auto ld = [&](bool p, int o) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, p ? o : -1, 0, 0)); };
-#endif
     // the first voxel's value opens the walk: the entry crossing (on axis ax_in, when the ray enters through a real plane) is
     // added after the loop, the loop's first "dominant-axis crossing" then sees no jump
     const bool walks = live && ahi > alo;
@@ -495,7 +480,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_SLAB_
             off_next = off3 + sm;
         }
         const bool p1 = l1 > 0.f, p2 = l2 > 0.f, p3 = l3 > 0.f;
-#if !defined(XVR_SLAB_ABLATE)
         // The three loads of a slab under EXEC masks, back to back, in one asm block (written as branches the compiler chains each
         // load behind its predecessor's select).  A lane without the segment costs the texture-address unit nothing this way.
         // Until late in round 4 such a lane passed the buffer resource an out-of-range offset instead (0 back, no memory
@@ -521,11 +505,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_SLAB_
                          : [o1] "v"(off), [o2] "v"(off2), [o3] "v"(off3), [rs] "s"(rsrc), [m1] "s"(m1), [m2] "s"(m2), [m3] "s"(m3)
                          : "memory", "scc");
         }
-#define XVR_SLAB_WAIT_LOADS() asm volatile("s_waitcnt vmcnt(0)" : "+v"(t1), "+v"(t2), "+v"(t3))
-#else
-        float t1 = ld(p1, off), t2 = ld(p2, off2), t3 = ld(p3, off3);
-#define XVR_SLAB_WAIT_LOADS() ((void)0)
-#endif
         if (A.work) cnt += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(p1)) + (unsigned)__popcll(__builtin_amdgcn_ballot_w64(p2)) +
                            (unsigned)__popcll(__builtin_amdgcn_ballot_w64(p3));
         // (what does not need the loaded values, while they are in flight)
@@ -535,7 +514,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_SLAB_
         fpm += stm;
         if (!NX) off = off_next;
         ac = aend;
-        XVR_SLAB_WAIT_LOADS();
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(t1), "+v"(t2), "+v"(t3));   // (the asm block's loads: the compiler does not count them)
         if (!JAC) {
             acc = fmaf(p1 ? t1 : 0.f, l1, acc);
             acc = fmaf(p2 ? t2 : 0.f, l2, acc);
@@ -658,8 +637,7 @@ int xvr_drr_siddon_backward(const float* volume, const float* mask, int D0, int 
                             const float* source, const float* target, const float* raylen, int B, int n,
                             const xvr_drr_spec* sp, const float* grad_out, float* grad_volume,
                             float* grad_source, float* grad_target, float* grad_raylen, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-
+                            size_t workspace_bytes, void* stream, int slab_index, int slab_count) {
     int rc = check_common(volume, D0, D1, D2, C, source, target, raylen, B, n, sp);
     if (rc) return rc;
     if (!grad_out) return fail(XVR_DRR_E_ARG, "grad_out is null");
@@ -693,8 +671,9 @@ int xvr_drr_siddon_backward(const float* volume, const float* mask, int D0, int 
     if (gvol && ((!mask && (exact_geom || cells || splat)) || (mask && exact_geom)) && gather_usable(sp, n, workspace, workspace_bytes, B, D0, D1, D2)) {
         unsigned* flag = nullptr;
         rc = launch_gather(true, source, target, raylen, grad_out, B, n, sp->ray_grid_w, D0, D1, D2, sp, grad_volume,
-                           workspace, stream, &flag, mask, C, exact_geom ? nullptr : olo, splat ? (exact_geom ? 1 : 2) : 0);
-        if (rc || gather_slab_later()) return rc;
+                           workspace, stream, &flag, slab_index, slab_count, mask, C, exact_geom ? nullptr : olo,
+                           splat ? (exact_geom ? 1 : 2) : 0);
+        if (rc || gather_slab_later(slab_index, slab_count)) return rc;
         RenderArgs Ap = A, Av = A;
         Ap.gvol = nullptr;
         Av.gsrc = nullptr; Av.gtgt = nullptr; Av.glen = nullptr;
@@ -710,7 +689,7 @@ int xvr_drr_siddon_backward(const float* volume, const float* mask, int D0, int 
         if (gpose) { rc = launch(k_siddon<2, false, true, false, false>, Ap, 0, stream); if (rc) return rc; }
         return launch(k_siddon<2, false, false, true, false>, Av, 0, stream);
     }
-    if (gather_slab_later()) return XVR_DRR_OK;   // (option gather_slab: the call for slab 0 did everything)
+    if (gather_slab_later(slab_index, slab_count)) return XVR_DRR_OK;   // (the call for slab 0 did everything)
 #define SID_BWD2(M, E)                                                                  \
     (gpose ? (gvol ? launch(k_siddon<2, M, true, true, E>, A, lds, stream)              \
                    : launch(k_siddon<2, M, true, false, E>, A, lds, stream))            \

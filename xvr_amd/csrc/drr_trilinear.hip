@@ -47,11 +47,9 @@ struct SlabRange {
 
 // WIN (clip_to_volume == 2, with the jacobian): also E1 = sum (alpha_k - A) (a d . grad V) -- d out / d (window width) needs it
 // directly; rebuilt from G and H it is a difference of two large sums and loses 2 % in float32
-#ifndef XVR_FWD_MASK_REGS   // 0: per-lane LDS accumulators for any C (the product); 1: up to eight label channels summed in registers --
-                            // round 6 A/B at C5 (tools/ab_mask_regs.sh): 6.47 against 5.87 ms (forward), 7.21 against 6.63 (+ jacobian):
-                            // the eight predicated adds per sample cost more issue slots than the LDS round trip costs latency
-#define XVR_FWD_MASK_REGS 0
-#endif
+// The label channels are summed in per-lane LDS accumulators for any C.  Up to eight channels summed in registers instead lost
+// the round 6 A/B at C5: 6.47 against 5.87 ms (forward), 7.21 against 6.63 (+ jacobian) -- the eight predicated adds per sample
+// cost more issue slots than the LDS round trip costs latency.
 template <bool JAC, int MASK, bool CLIP, int YP = 0, bool SLAB = false, bool WIN = false, int SYNC = 0>
 __device__ __forceinline__ void tri_march(const RenderArgs& A, const Ray& R, const KRange K, const int kbeg, const int kend,
                                           const float step, const SpecWin Wn, float* lds, const int tid, TriAcc& acc,
@@ -63,16 +61,12 @@ __device__ __forceinline__ void tri_march(const RenderArgs& A, const Ray& R, con
     float G[3] = {0.f, 0.f, 0.f}, H[3] = {0.f, 0.f, 0.f};
     float E0 = 0.f, E1 = 0.f;
     unsigned cnt = 0;
-#if XVR_FWD_MASK_REGS
-    const bool ch_regs = MASK && A.C <= 8;   // (uniform)
-    float ch[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#endif
     const float adx = A.sp.a[0] * R.d[0], ady = A.sp.a[1] * R.d[1], adz = A.sp.a[2] * R.d[2];
 
     // Two steps per trip: the 8 independent 8-byte gathers of both samples are issued before either
     // is consumed (the march is latency-bound, not bandwidth-bound: L2 at ~20 %, HBM at ~25 %).
     for (int kk = kbeg; kk <= kend; kk += 2) {
-        // SYNC: the wavefronts of a workgroup march a common step range and meet every SYNC trips (XVR_FWD_SYNC below)
+        // SYNC: the wavefronts of a workgroup march a common step range and meet every SYNC trips (FWD_SYNC below)
         if (SYNC && (((kk - kbeg) >> 1) % SYNC) == 0) __builtin_amdgcn_s_barrier();
         bool act[2];
         float u[2], al[2], pxs[2], pys[2], pzs[2];
@@ -157,14 +151,6 @@ __device__ __forceinline__ void tri_march(const RenderArgs& A, const Ray& R, con
             const float v = fmaf(t.wx1, r1, t.wx0 * r0);
             ++cnt;
             if (MASK) {
-#if XVR_FWD_MASK_REGS
-                if (ch_regs) {
-                    // (diagnostic build) up to eight channels: the sums stay in registers -- eight predicated adds instead of an LDS
-                    // read-modify-write
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) ch[c] += lab == c ? v : 0.f;
-                } else
-#endif
                 lds[lab * WG + tid] += v;
                 if (JAC) S += v;  // the jacobian saved with a mask is that of the channel SUM
             } else {
@@ -190,13 +176,6 @@ __device__ __forceinline__ void tri_march(const RenderArgs& A, const Ray& R, con
         if (__builtin_amdgcn_ballot_w64(inside) == ~0ull) trip(std::true_type{});
         else trip(std::false_type{});
     }
-#if XVR_FWD_MASK_REGS
-    if (MASK && ch_regs) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            if (c < A.C) lds[c * WG + tid] += ch[c];
-    }
-#endif
     acc.S = S;
     acc.cnt = cnt;
 #pragma unroll
@@ -251,18 +230,13 @@ __device__ __forceinline__ void tri_finish(const RenderArgs& A, const Ray& R, co
 // 8 wavefronts per SIMD and took 8.2 ms where the (heavier) jacobian variant at 6 took 7.0; capped, both take
 // ~7.0 ms (measured flat from 3 to 6, worse at 2 and at 8).
 constexpr double SLAB_TARGET_BYTES = 150e6, SLAB_MIN_VOLUME_BYTES = 192.0 * (1 << 20);   // (the Infinity Cache holds 256 MiB)
-// XVR_FWD_SYNC (round 3): the four wavefronts of a workgroup march a COMMON step range and meet at a barrier every SYNC trips
+// FWD_SYNC (round 3): the four wavefronts of a workgroup march a COMMON step range and meet at a barrier every SYNC trips
 // (a trip = two samples), so that the 8x8 patches of one 16x16 tile touch the cache lines they share while those are in the
 // L1.  C2, forward + jacobian: 6.04 ms without, 5.69 at 1, 5.69 at 4, 5.79 at 16 (profiles/r03_forward_sync.txt); two or four
 // tiles per workgroup of 512 / 1024 threads in lockstep: 5.83 / 7.90 (one workgroup per CU leaves nothing to overlap).
-#ifndef XVR_FWD_SYNC
-#define XVR_FWD_SYNC 1
-#endif
-#ifndef XVR_FWD_WAVES   // (overridable for tuning builds)
-#define XVR_FWD_WAVES 4
-#endif
+constexpr int FWD_SYNC = 1, FWD_WAVES = 4;
 template <bool JAC, int MASK, bool CLIP, int YP = 0, bool WIN = false>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_FWD_WAVES))) void k_trilinear_fwd(RenderArgs A) {
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, FWD_WAVES))) void k_trilinear_fwd(RenderArgs A) {
     extern __shared__ float lds[];  // MASK: per-lane channel accumulators [C][WG]
     int b, r;
     const bool valid = map_ray(A, b, r, threadIdx.x);
@@ -275,7 +249,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_FWD_W
     const KRange K = tri_krange(A, R, CLIP, step, Wn.near_);
     int kbeg = __builtin_amdgcn_readfirstlane(wave_min_i(K.lo));
     int kend = __builtin_amdgcn_readfirstlane(wave_max_i(K.hi));
-#if XVR_FWD_SYNC
     __shared__ int s_k[2];
     if (tid == 0) { s_k[0] = 0x7fffffff; s_k[1] = -0x7fffffff; }
     __syncthreads();
@@ -283,12 +256,11 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_FWD_W
     __syncthreads();
     kbeg = __builtin_amdgcn_readfirstlane(s_k[0]);
     kend = __builtin_amdgcn_readfirstlane(s_k[1]);
-#endif
     if (MASK) {
         for (int c = 0; c < A.C; ++c) lds[c * WG + tid] = 0.f;
     }
     TriAcc acc;
-    tri_march<JAC, MASK, CLIP, YP, false, WIN, XVR_FWD_SYNC>(A, R, K, kbeg, kend, step, Wn, lds, tid, acc);
+    tri_march<JAC, MASK, CLIP, YP, false, WIN, FWD_SYNC>(A, R, K, kbeg, kend, step, Wn, lds, tid, acc);
     if (valid) tri_finish<JAC, MASK, CLIP, WIN>(A, R, b, r, Wn, lds, tid, acc);
     if (A.work) {
         unsigned tot = wave_sum_u(acc.cnt);
@@ -314,7 +286,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_FWD_W
 // kernel are bit-identical to each other).
 // ---------------------------------------------------------------------------------------------
 template <bool JAC, bool YP>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, XVR_FWD_WAVES))) void k_trilinear_fwd_slab(RenderArgs A, int slab, int nslabs,
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(1, FWD_WAVES))) void k_trilinear_fwd_slab(RenderArgs A, int slab, int nslabs,
                                                                                                            SlabRange S) {
     int b, r;
     const bool valid = map_ray(A, b, r, threadIdx.x);
@@ -885,7 +857,7 @@ int xvr_drr_trilinear_backward(const float* volume, const float* mask, int D0, i
                                const float* source, const float* target, const float* raylen, int B, int n,
                                const xvr_drr_spec* sp, const float* grad_out, float* grad_volume,
                                float* grad_source, float* grad_target, float* grad_raylen, void* workspace,
-                               size_t workspace_bytes, void* stream) {
+                               size_t workspace_bytes, void* stream, int slab_index, int slab_count) {
     int rc = check_common(volume, D0, D1, D2, C, source, target, raylen, B, n, sp);
     if (rc) return rc;
     if (!grad_out) return fail(XVR_DRR_E_ARG, "grad_out is null");
@@ -911,12 +883,12 @@ int xvr_drr_trilinear_backward(const float* volume, const float* mask, int D0, i
     // table kernel for the plain render, the pixel-major kernel under clip_to_volume and / or a mask; the scatter kernel
     // stays as the general fallback and is launched right behind it, reading the lattice flag on the device (no host sync).
     const bool gather = gvol && gather_usable(sp, n, workspace, workspace_bytes, B, D0, D1, D2);
-    if (gather_slab_later() && !gather) return XVR_DRR_OK;   // (option gather_slab: the call for slab 0 did everything)
+    if (gather_slab_later(slab_index, slab_count) && !gather) return XVR_DRR_OK;   // (the call for slab 0 did everything)
     if (gather) {
         unsigned* flag = nullptr;
         rc = launch_gather(false, source, target, raylen, grad_out, B, n, sp->ray_grid_w, D0, D1, D2, sp, grad_volume,
-                           workspace, stream, &flag, mask, C);
-        if (rc || gather_slab_later()) return rc;
+                           workspace, stream, &flag, slab_index, slab_count, mask, C);
+        if (rc || gather_slab_later(slab_index, slab_count)) return rc;
         RenderArgs Ap = A, Av = A;
         Ap.gvol = nullptr;
         Av.gsrc = nullptr; Av.gtgt = nullptr; Av.glen = nullptr;

@@ -134,7 +134,7 @@ def allreduce_volume_grad_bucketed(grad: torch.Tensor, n_buckets: int = 8, force
 
 class SlabAllReduce:
     """The voxel-gradient sum of a fwd+bwd(pose+voxel) step, OVERLAPPED with the backward that produces it: while installed, the
-    renderer computes the voxel gradient in ``count`` x slabs (xvr_amd.renderers.VOXEL_GRAD_SLABS, option gather_slab of the library)
+    renderer computes the voxel gradient in ``count`` x slabs (xvr_amd.renderers.VOXEL_GRAD_SLABS, arguments slab_index / slab_count of the library's backward)
     and every finished slab goes into an async all-reduce at once -- RCCL moves slab i over xGMI while the splat works on slab i + 1;
     only the last slab's collective is exposed.
 

@@ -446,27 +446,23 @@ class _Render(torch.autograd.Function):
                 # (the per-cell scratch only when the cells gather will really run: Siddon, no mask left, rays on a lattice)
                 ws, ws_bytes = _workspace(lib, B, n, (D0, D1, D2), dev, cs,
                                           cells=spec.renderer == "siddon" and msk_c is None and ctx.ray_grid_w > 1)
-            def call():
+            def call(i=0, count=0):
                 return fn(_ptr(vol_c), _ptr(msk_c), D0, D1, D2, C, _ptr(src_c), _ptr(tgt_c), _ptr(len_c), B, n,
                           ctypes.byref(cs), _ptr(gout), _ptr(gvol),
                           _ptr(gsrc) if pose_here else None, _ptr(gtgt) if pose_here else None,
-                          _ptr(glen) if pose_here else None, _ptr(ws), ws_bytes, _stream())
+                          _ptr(glen) if pose_here else None, _ptr(ws), ws_bytes, _stream(), i, count)
 
             def call_in_slabs(count, hook):
-                # the voxel gradient in x slabs of whole brick planes, one call per slab (option gather_slab): slab i is complete
+                # the voxel gradient in x slabs of whole brick planes, one call per slab (slab_index, slab_count): slab i is complete
                 # when call i has been issued, and the hook may hand it to a collective while call i + 1 runs
                 nb0 = (D0 + 15) // 16
-                try:
-                    for i in range(count):
-                        _lib.set_option("gather_slab", i | (count << 8))
-                        rc = call()
-                        if rc:
-                            return rc
-                        x0, x1 = min(16 * (i * nb0 // count), D0), min(16 * ((i + 1) * nb0 // count), D0)
-                        if hook is not None and x1 > x0:
-                            hook(i, gvol[x0:x1])
-                finally:
-                    _lib.set_option("gather_slab", 0)
+                for i in range(count):
+                    rc = call(i, count)
+                    if rc:
+                        return rc
+                    x0, x1 = min(16 * (i * nb0 // count), D0), min(16 * ((i + 1) * nb0 // count), D0)
+                    if hook is not None and x1 > x0:
+                        hook(i, gvol[x0:x1])
                 return 0
 
             slabs = VOXEL_GRAD_SLABS if (need_vol and ws is not None and gvol.dim() == 3) else None
