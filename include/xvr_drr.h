@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define XVR_DRR_ABI_VERSION 12   /* 12: xvr_drr_trilinear_backward / xvr_drr_siddon_backward take slab_index, slab_count (an argument of the call where a process-wide option used to carry it); 11: xvr_sim_augment_* (the training step's X-ray augmentations); 10: xvr_sim_ncc_registration_step (the tail of a registration iteration in the similarity's launches); 9: xvr_drr_pack_hu_labels_ytiles, options siddon_splat / gather_splat = 3 / siddon_slab = 2, pose kind 6 (rotation_10d), non-exact Siddon index maps on the slab march and the brick splat, guard-banded fixed point; 8: volume_layout 3 + xvr_drr_pack_ytiles / _labels_ytiles (tiled y-pair copy), xvr_pose_camera_forward_param / xvr_pose_opt_step_param (device-resident registration for every parameterisation; xvr_pose_opt_state holds 13 parameters), xvr_sim_equalize_* write / take the normalised output, options tile_geom, siddon_slab, siddon_gather_fast; 7: xvr_drr_foreground, xvr_drr_pack_labels_ypairs, xvr_sim_dice_bool, xvr_sim_transform_* (xvr_sim.h), xvr_pose_convert_* (xvr_pose.h); 6: xvr_drr_spec.alpha_window + xvr_drr_alpha_window (clip_to_volume = 2); 5: xvr_drr_set_option / xvr_drr_get_option (the A/B switches are no longer getenv calls per launch); 4: volume_layout 2 + xvr_drr_pack_bricks (siddon forward); 3: xvr_drr_spec.volume_layout + xvr_drr_pack_ypairs; 2: xvr_sim_spec grew, camera-driven forwards, packed labels, xvr_pose.h */
+#define XVR_DRR_ABI_VERSION 12   /* (xvr_drr_jac_to_pose_backward was ADDED under 12: no existing entry point changed shape) 12: xvr_drr_trilinear_backward / xvr_drr_siddon_backward take slab_index, slab_count (an argument of the call where a process-wide option used to carry it); 11: xvr_sim_augment_* (the training step's X-ray augmentations); 10: xvr_sim_ncc_registration_step (the tail of a registration iteration in the similarity's launches); 9: xvr_drr_pack_hu_labels_ytiles, options siddon_splat / gather_splat = 3 / siddon_slab = 2, pose kind 6 (rotation_10d), non-exact Siddon index maps on the slab march and the brick splat, guard-banded fixed point; 8: volume_layout 3 + xvr_drr_pack_ytiles / _labels_ytiles (tiled y-pair copy), xvr_pose_camera_forward_param / xvr_pose_opt_step_param (device-resident registration for every parameterisation; xvr_pose_opt_state holds 13 parameters), xvr_sim_equalize_* write / take the normalised output, options tile_geom, siddon_slab, siddon_gather_fast; 7: xvr_drr_foreground, xvr_drr_pack_labels_ypairs, xvr_sim_dice_bool, xvr_sim_transform_* (xvr_sim.h), xvr_pose_convert_* (xvr_pose.h); 6: xvr_drr_spec.alpha_window + xvr_drr_alpha_window (clip_to_volume = 2); 5: xvr_drr_set_option / xvr_drr_get_option (the A/B switches are no longer getenv calls per launch); 4: volume_layout 2 + xvr_drr_pack_bricks (siddon forward); 3: xvr_drr_spec.volume_layout + xvr_drr_pack_ypairs; 2: xvr_sim_spec grew, camera-driven forwards, packed labels, xvr_pose.h */
 
 #define XVR_DRR_OK 0
 #define XVR_DRR_E_ARG (-1)     /* bad argument (null pointer, non-positive size, unsupported combo) */
@@ -327,6 +327,20 @@ int xvr_drr_pack_bricks(const float* volume, int D0, int D1, int D2, float* bric
 size_t xvr_drr_jac_to_camera_workspace_bytes(int B, int H, int W);
 int xvr_drr_jac_to_camera_backward(const float* jac, const float* grad_out, const float* cam, int B, int H, int W,
                                    float* grad_cam, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Jacobian -> pose parameters in one pass: xvr_drr_jac_to_camera_backward extended by the camera -> parameter step
+ * (= xvr_drr_backward_from_jac, xvr_drr_rays_backward and xvr_pose_camera_backward / xvr_pose_convert_backward in one launch), for
+ * callers whose rays were generated from cam [B][24] = G vec(M[:3,:4]) + c with the pose matrix M evaluated on the device
+ * (xvr_pose_camera_forward / xvr_pose_camera_forward_param, xvr_pose.h).
+ *   kind 0: rot [B][3] Euler angles in the convention `axes`; kind 1..6: rot [B][k] and pose_jac as written by
+ *   xvr_pose_camera_forward_param (NULL for kind 0)  ->  grad_rot [B][k], grad_xyz [B][3] WRITTEN; grad_cam [B][24] too unless NULL
+ * Same fixed-order sums and the same workspace contract as xvr_drr_jac_to_camera_backward (zero-filled once, left ready).
+ */
+int xvr_drr_jac_to_pose_backward(const float* jac, const float* grad_out, const float* cam, int B, int H, int W, const float* rot,
+                                 const float* xyz, int kind, const int axes[3], const float* G, const float* pose_jac,
+                                 float* grad_rot, float* grad_xyz, float* grad_cam, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 
 /*
  * HU -> density of a whole CT.  Replaces diffdrr.data.transform_hu_to_density(volume, multiplier), which

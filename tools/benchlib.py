@@ -152,7 +152,8 @@ TRAFFIC_KERNELS = {
     "trilinear_backward": ["k_trilinear_splat_b16", "k_trilinear_gather_tab", "k_gather_prep", "k_gather_cull", "k_trilinear_bwd"],
     "siddon_forward": ["k_siddon<", "k_siddon_slab"],
     "siddon_backward": ["k_siddon_gather_vol", "k_gather_prep", "k_gather_cull", "k_siddon<"],
-    "backward_from_jac": ["k_backward_from_jac"],
+    "backward_from_jac": ["k_backward_from_jac"],       # (callers that pass source / target tensors; the benchmark's step no longer emits it)
+    "jac_to_pose_backward": ["k_jac_to_cam<4, true>", "k_jac_to_cam<1, true>"],   # the one-launch pose tail (no PMC pass committed yet: None)
 }
 
 

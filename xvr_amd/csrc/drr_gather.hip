@@ -273,9 +273,9 @@ __device__ __forceinline__ void brick_coords(int blk, int D1, int D2, const int*
 // (bounding sphere against the pose's sample pyramid, conservative).  32 poses per word.
 __global__ __launch_bounds__(WG) void k_gather_cull(GatherArgs G, int nbricks) {
     if (G.only_if_fine >= 0 && (int)(G.flag[3] != 0u) != G.only_if_fine) return;   // (the kernel pair of the other regime runs instead)
-    const int brick = blockIdx.x * (WG / 32) + (threadIdx.x >> 5);
     const int lane = threadIdx.x & 31;
-    if (brick >= nbricks) return;
+    // (grid-stride over the bricks: one trip under a full grid; the not-taken regime's launch is a few resident workgroups, not a grid)
+    for (int brick = blockIdx.x * (WG / 32) + (threadIdx.x >> 5); brick < nbricks; brick += gridDim.x * (WG / 32)) {
     int bx, by, bz;
     brick_coords(brick, G.D1, G.D2, G.bd, bx, by, bz);
     const float c[3] = {bx * G.bd[0] + 0.5f * (G.bd[0] - 1), by * G.bd[1] + 0.5f * (G.bd[1] - 1),
@@ -323,6 +323,7 @@ __global__ __launch_bounds__(WG) void k_gather_cull(GatherArgs G, int nbricks) {
         const unsigned long long m = __ballot(hit);
         const unsigned bits = (threadIdx.x & 32) ? (unsigned)(m >> 32) : (unsigned)m;
         if (lane == 0) G.cull[(size_t)brick * G.words + wd] = bits;
+    }
     }
 }
 
@@ -437,33 +438,39 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TAB_WAVES, T
     if (G.only_if_fine >= 0 && (int)(G.flag[3] != 0u) != G.only_if_fine) return;   // (the splat took the launch)
     __shared__ uint2 tab[TAB_ROWS * 64];
     constexpr float HS = 1.5f, CO = 0.5f;
-    int bx, by, bz;
-    brick_coords(blockIdx.x, G.D1, G.D2, G.bd, bx, by, bz);
     const int tid = threadIdx.x;  // one wavefront: 4 x 4 x 4 blocks of 2 x 2 x 2 voxels
-    const int vx = (bx * 4 + (tid >> 4)) * 2, vy = (by * 4 + ((tid >> 2) & 3)) * 2, vz = (bz * 4 + (tid & 3)) * 2;
-    const bool inb = vx < G.D0 && vy < G.D1 && vz < G.D2;
-    const float fv[3] = {(float)vx, (float)vy, (float)vz};
-    float xv[3];  // block centre in x coordinates
-#pragma unroll
-    for (int i = 0; i < 3; ++i) xv[i] = (fv[i] + CO - G.sp.b[i]) / G.sp.a[i];
     const int N = G.sp.n_points;
     const float near_ = spec_window(G.sp).near_, far_ = spec_window(G.sp).far_;
     const float step = N > 1 ? (far_ - near_) / (float)(N - 1) : 0.f;
     const float inv_step = step > 0.f ? 1.f / step : 0.f;
     const float a0 = G.sp.a[0], a1 = G.sp.a[1], a2 = G.sp.a[2];
     const float b0 = G.sp.b[0], b1 = G.sp.b[1], b2 = G.sp.b[2];
-    const float bv0 = b0 - fv[0], bv1 = b1 - fv[1], bv2 = b2 - fv[2];
     const float jmargin = GATHER_DEV_TOL + 0.01f;
     const float Hm1 = (float)(G.H - 1), Wm1 = (float)(G.W - 1);
 #ifdef XVR_GATHER_STATS
     unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
+    // Grid-stride over the bricks.  Launched as THE gather (gather_splat = 0) the grid is one workgroup per brick and the loop has one
+    // trip; launched behind the splat as the regime that is usually not taken, the grid is what is resident at once, so that not
+    // being taken costs a few thousand wavefronts that read the flag line instead of one per brick.  A brick's arithmetic and the
+    // order of its sums do not depend on which workgroup takes it (the table is lane-private: no barrier between bricks).
+    const unsigned nblk = (unsigned)(((G.D0 + G.bd[0] - 1) / G.bd[0]) * ((G.D1 + G.bd[1] - 1) / G.bd[1]) * ((G.D2 + G.bd[2] - 1) / G.bd[2]));
+    for (unsigned blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    int bx, by, bz;
+    brick_coords((int)blk, G.D1, G.D2, G.bd, bx, by, bz);
+    const int vx = (bx * 4 + (tid >> 4)) * 2, vy = (by * 4 + ((tid >> 2) & 3)) * 2, vz = (bz * 4 + (tid & 3)) * 2;
+    const bool inb = vx < G.D0 && vy < G.D1 && vz < G.D2;
+    const float fv[3] = {(float)vx, (float)vy, (float)vz};
+    float xv[3];  // block centre in x coordinates
+#pragma unroll
+    for (int i = 0; i < 3; ++i) xv[i] = (fv[i] + CO - G.sp.b[i]) / G.sp.a[i];
+    const float bv0 = b0 - fv[0], bv1 = b1 - fv[1], bv2 = b2 - fv[2];
     float acc[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = 0.f;
 
     for (int wd = 0; wd < G.words; ++wd) {
-        unsigned bits = G.cull[(size_t)blockIdx.x * G.words + wd];  // uniform: scalar load
+        unsigned bits = G.cull[(size_t)blk * G.words + wd];  // uniform: scalar load
         while (bits) {
             const int p = wd * 32 + __builtin_ctz(bits);
             bits &= bits - 1;
@@ -618,11 +625,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TAB_WAVES, T
             }
         }
     }
+    add_block8(G.gvol, acc, vx, vy, vz, G.D0, G.D1, G.D2);
+    }
 #ifdef XVR_GATHER_STATS
     for (int i = 0; i < 8; ++i)
         if (st[i]) atomicAdd(&g_gather_stats[i], st[i]);
 #endif
-    add_block8(G.gvol, acc, vx, vy, vz, G.D0, G.D1, G.D2);
 }
 
 #include "drr_splat.hiph"   // k_trilinear_splat_b16, k_trilinear_splat_px: the brick-local fixed-point splats (the default)
@@ -1461,8 +1469,23 @@ int xvr_detail::launch_gather(bool siddon, const float* source, const float* tar
             T.bd[0] = T.bd[1] = T.bd[2] = 4 * T.V;
             T.cull = G.cull + (size_t)bricks * G.words;
             const long long tb = n_bricks(D0, D1, D2, T.bd);
-            hipLaunchKernelGGL(k_gather_cull, dim3((unsigned)((tb + WG / 32 - 1) / (WG / 32))), dim3(WG), 0, (hipStream_t)stream, T, (int)tb);
-            hipLaunchKernelGGL(k_trilinear_gather_tab, dim3((unsigned)tb), dim3(64), 0, (hipStream_t)stream, T);
+            // Both are grid-stride kernels launched with what is resident at once (CUs x occupancy), not with one workgroup per brick:
+            // in the regime that is not taken -- the usual one -- every workgroup reads the flag line and leaves, and a full grid of
+            // 2.6e5 wavefronts doing that cost 0.07 ms per step at 512^3.  (XVR_FULL_GRID_FALLBACKS: the full grids, for the test
+            // that compares the two dispatches bit for bit.)
+            long long cull_wgs = (tb + WG / 32 - 1) / (WG / 32), tab_wgs = tb;
+#ifndef XVR_FULL_GRID_FALLBACKS
+            static const int tab_resident = [] {
+                int per_cu = 0, dev = 0, cus = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trilinear_gather_tab, 64, 0) != hipSuccess || per_cu < 1) per_cu = 4 * TAB_WAVES;
+                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+                return per_cu * cus;
+            }();
+            if (tab_wgs > tab_resident) tab_wgs = tab_resident;
+            if (cull_wgs > tab_resident / 4) cull_wgs = tab_resident / 4;   // (256-thread workgroups)
+#endif
+            hipLaunchKernelGGL(k_gather_cull, dim3((unsigned)cull_wgs), dim3(WG), 0, (hipStream_t)stream, T, (int)tb);
+            hipLaunchKernelGGL(k_trilinear_gather_tab, dim3((unsigned)tab_wgs), dim3(64), 0, (hipStream_t)stream, T);
         }
         // persistent workgroups: as many as run at once (the occupancy the runtime reports x the CUs), never more than bricks
         static const int resident = [] {

@@ -2,6 +2,7 @@
 // from the camera vector and its adjoint, jacobian -> camera in one fixed-order pass.
 #include "drr_common.hiph"
 #include "j2c_device.hiph"
+#include "pose_device.hiph"
 
 namespace {
 
@@ -156,10 +157,24 @@ __global__ __launch_bounds__(WG) void k_rays_bwd(const float* __restrict__ cam, 
 // RPT = rays per thread (ray base + t + k WG of the block's WG * RPT): 1 for registration-sized launches (latency: as many
 // blocks as possible); 4 for batches -- a quarter of the 24 wavefront reductions, stores and tickets per ray, all 12 loads of
 // a thread in flight at once (C2, 116 poses: 0.32 -> see profiles/r03_bench_final_pose_only.json)
-template <int RPT>
+// POSE: the camera -> parameter step of k_pose_camera_bwd / k_pose_convert_bwd as the epilogue of the block that draws a pose's last
+// ticket (xvr_drr_jac_to_pose_backward, below); the loads, the accumulation and the reduction are the same code either way.
+struct J2PArgs {
+    const float* rot;        // [B][k]
+    const float* xyz;        // [B][3]
+    const float* G;          // [24][12]
+    const float* pose_jac;   // kind != 0: [B][12][XVR_POSE_MAX_PARAMS] as stored by xvr_pose_camera_forward_param
+    float* g_rot;
+    float* g_xyz;
+    int kind, k;
+    Axes ax;
+};
+
+template <int RPT, bool POSE>
 __global__ __launch_bounds__(WG) void k_jac_to_cam(const float* __restrict__ jac, const float* __restrict__ gout,
                                                    const float* __restrict__ cam, int H, int W, float* partial,
-                                                   unsigned* counter, float* __restrict__ g_cam) {
+                                                   unsigned* counter, float* __restrict__ g_cam, J2PArgs P) {
+    __shared__ float gc[24];
     const int b = blockIdx.y, n = H * W, nblk = gridDim.x;
     const float* c = cam + 24 * b;
     float acc[24];
@@ -185,7 +200,34 @@ __global__ __launch_bounds__(WG) void k_jac_to_cam(const float* __restrict__ jac
         const int r = (blockIdx.x * RPT + k) * WG + threadIdx.x;
         if (r < n) j2c_accumulate(g_[k], j0_[k], j1_[k], c, r, W, acc);
     }
-    j2c_reduce(acc, partial, counter, b, nblk, g_cam + 24 * b);
+    if (!POSE) {
+        j2c_reduce(acc, partial, counter, b, nblk, g_cam + 24 * b);
+        return;
+    }
+    if (!j2c_reduce(acc, partial, counter, b, nblk, gc)) return;
+    if (g_cam && threadIdx.x < 24) g_cam[24 * b + threadIdx.x] = gc[threadIdx.x];
+    if (threadIdx.x >= 64) return;   // one wavefront per pose from here, as in k_pose_camera_bwd
+    float gm[12];
+    wave_gt_g(P.G, gc, false, gm);
+    if (P.kind == 0) {
+        float gth[3], gt[3];
+        const float th[3] = {P.rot[b * 3], P.rot[b * 3 + 1], P.rot[b * 3 + 2]};
+        const float t[3] = {P.xyz[b * 3], P.xyz[b * 3 + 1], P.xyz[b * 3 + 2]};
+        pose_chain(P.ax, th, t, gm, gth, gt);
+        if (threadIdx.x < 3) {
+            P.g_rot[b * 3 + threadIdx.x] = gth[threadIdx.x];
+            P.g_xyz[b * 3 + threadIdx.x] = gt[threadIdx.x];
+        }
+    } else {
+        const int d = threadIdx.x;   // one lane per parameter: J^T g_m in k_pose_convert_bwd's order
+        if (d < P.k + 3) {
+            const float* J = P.pose_jac + (size_t)b * 12 * XVR_POSE_MAX_PARAMS;
+            float sum = 0.f;
+            for (int e = 0; e < 12; ++e) sum = fmaf(J[e * XVR_POSE_MAX_PARAMS + d], gm[e], sum);
+            if (d < P.k) P.g_rot[(size_t)b * P.k + d] = sum;
+            else P.g_xyz[(size_t)b * 3 + (d - P.k)] = sum;
+        }
+    }
 }
 
 // =============================================================================================
@@ -413,24 +455,51 @@ size_t xvr_drr_jac_to_camera_workspace_bytes(int B, int H, int W) {
     return align256((size_t)B * sizeof(unsigned)) + (size_t)B * nblk * 24 * sizeof(float);
 }
 
-int xvr_drr_jac_to_camera_backward(const float* jac, const float* grad_out, const float* cam, int B, int H, int W,
-                                   float* grad_cam, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!jac || !grad_out || !cam || !grad_cam || !workspace) return fail(XVR_DRR_E_ARG, "null pointer argument");
+// the one launch behind xvr_drr_jac_to_camera_backward and xvr_drr_jac_to_pose_backward (P: null = camera only)
+static int j2c_launch(const float* jac, const float* grad_out, const float* cam, int B, int H, int W, float* grad_cam,
+                      void* workspace, size_t workspace_bytes, void* stream, const J2PArgs* P) {
     if (B <= 0 || H <= 0 || W <= 0) return fail(XVR_DRR_E_ARG, "B, H, W must be positive");
     if (workspace_bytes < xvr_drr_jac_to_camera_workspace_bytes(B, H, W)) return fail(XVR_DRR_E_ARG, "workspace too small");
     if (reinterpret_cast<uintptr_t>(jac) & 15u) return fail(XVR_DRR_E_ARG, "jac must be 16-byte aligned");
     const bool batch = (size_t)B * H * W >= ((size_t)1 << 20);   // (a registration iteration: one to eight 256^2 ... 512^2 images)
     const unsigned per_block = batch ? 4 * WG : WG;
-    const unsigned nblk = (unsigned)(((size_t)H * W + per_block - 1) / per_block);
+    const dim3 grid((unsigned)(((size_t)H * W + per_block - 1) / per_block), (unsigned)B);
     char* ws = static_cast<char*>(workspace);
     float* partial = reinterpret_cast<float*>(ws + align256((size_t)B * sizeof(unsigned)));
-    if (batch) hipLaunchKernelGGL(k_jac_to_cam<4>, dim3(nblk, (unsigned)B), dim3(WG), 0, (hipStream_t)stream, jac, grad_out, cam, H, W, partial,
-                                  reinterpret_cast<unsigned*>(ws), grad_cam);
-    else hipLaunchKernelGGL(k_jac_to_cam<1>, dim3(nblk, (unsigned)B), dim3(WG), 0, (hipStream_t)stream, jac, grad_out, cam, H, W, partial,
-                            reinterpret_cast<unsigned*>(ws), grad_cam);
+    unsigned* counter = reinterpret_cast<unsigned*>(ws);
+    const hipStream_t st = (hipStream_t)stream;
+    const J2PArgs none = {};
+    if (P && batch) hipLaunchKernelGGL((k_jac_to_cam<4, true>), grid, dim3(WG), 0, st, jac, grad_out, cam, H, W, partial, counter, grad_cam, *P);
+    else if (P) hipLaunchKernelGGL((k_jac_to_cam<1, true>), grid, dim3(WG), 0, st, jac, grad_out, cam, H, W, partial, counter, grad_cam, *P);
+    else if (batch) hipLaunchKernelGGL((k_jac_to_cam<4, false>), grid, dim3(WG), 0, st, jac, grad_out, cam, H, W, partial, counter, grad_cam, none);
+    else hipLaunchKernelGGL((k_jac_to_cam<1, false>), grid, dim3(WG), 0, st, jac, grad_out, cam, H, W, partial, counter, grad_cam, none);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(XVR_DRR_E_LAUNCH, hipGetErrorString(e));
     return XVR_DRR_OK;
+}
+
+int xvr_drr_jac_to_camera_backward(const float* jac, const float* grad_out, const float* cam, int B, int H, int W,
+                                   float* grad_cam, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!jac || !grad_out || !cam || !grad_cam || !workspace) return fail(XVR_DRR_E_ARG, "null pointer argument");
+    return j2c_launch(jac, grad_out, cam, B, H, W, grad_cam, workspace, workspace_bytes, stream, nullptr);
+}
+
+int xvr_drr_jac_to_pose_backward(const float* jac, const float* grad_out, const float* cam, int B, int H, int W, const float* rot,
+                                 const float* xyz, int kind, const int axes[3], const float* G, const float* pose_jac,
+                                 float* grad_rot, float* grad_xyz, float* grad_cam, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    static const int POSE_K[7] = {3, 3, 4, 10, 6, 3, 10};   // rotation parameters of xvr_pose_convert_forward's kinds
+    if (!jac || !grad_out || !cam || !rot || !xyz || !G || !grad_rot || !grad_xyz || !workspace) return fail(XVR_DRR_E_ARG, "null pointer argument");
+    if (kind < 0 || kind > 6) return fail(XVR_DRR_E_ARG, "bad parameterisation");
+    J2PArgs P = {rot, xyz, G, pose_jac, grad_rot, grad_xyz, kind, POSE_K[kind], {{0, 1, 2}}};
+    if (kind == 0) {
+        if (!axes) return fail(XVR_DRR_E_ARG, "euler angles need a convention");
+        for (int i = 0; i < 3; ++i) {
+            if (axes[i] < 0 || axes[i] > 2) return fail(XVR_DRR_E_ARG, "axes must be 0, 1 or 2");
+            P.ax.a[i] = axes[i];
+        }
+    } else if (!pose_jac) return fail(XVR_DRR_E_ARG, "a non-Euler parameterisation needs the Jacobian xvr_pose_camera_forward_param stored");
+    return j2c_launch(jac, grad_out, cam, B, H, W, grad_cam, workspace, workspace_bytes, stream, &P);
 }
 
 int xvr_drr_rays_forward(const float* cam, int B, int H, int W, float* source, float* target, float* raylen,

@@ -612,9 +612,13 @@ __global__ __launch_bounds__(WG) void k_trilinear_bwd(RenderArgs A) {
     extern __shared__ float lds[];  // MASK: per-lane upstream gradient per channel [C][WG]
     // fallback role: when a gather launch precedes this one, run only if it declined (rays not a lattice)
     if (A.skip_unless_flag_gt && !(*A.skip_unless_flag_gt > __float_as_uint(GATHER_DEV_TOL))) return;
-    int b, r;
-    const bool valid = map_ray(A, b, r, threadIdx.x);
+    // grid-stride over the launch's logical blocks: one trip under a full grid; the fallback behind a gather is launched with what
+    // is resident at once (launch_fallback), so that declining costs those workgroups and not one per 256 rays
+    const unsigned nvb = (unsigned)A.B * (unsigned)A.blocks_per_pose;
     const int tid = threadIdx.x;
+    for (unsigned vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
+    int b, r;
+    const bool valid = map_ray(A, b, r, threadIdx.x, vb, nvb);
     Ray R;
     ray_setup(A, b, r, valid, R);
     const int N = A.sp.n_points;
@@ -724,8 +728,35 @@ __global__ __launch_bounds__(WG) void k_trilinear_bwd(RenderArgs A) {
             if ((tid & 63) == 0 && tot != 0.f) atomic_add_f32(A.gsrc + 3 * b + i, tot);
         }
     }
+    }
 }
 
+// The scatter kernel launched BEHIND a gather as its fallback (skip_unless_flag_gt set): as many workgroups as are resident at once,
+// walking the logical blocks grid-stride.  (XVR_FULL_GRID_FALLBACKS: the full grid, for the test that compares the two dispatches.)
+template <typename Kern>
+int launch_fallback(Kern kern, const RenderArgs& A, size_t lds_bytes, void* stream) {
+#ifdef XVR_FULL_GRID_FALLBACKS
+    return launch(kern, A, lds_bytes, stream);
+#else
+    const long long nblocks = (long long)A.B * A.blocks_per_pose;
+    if (nblocks >= (1LL << 31)) return fail(XVR_DRR_E_UNSUPPORTED, "grid too large");
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return fail(XVR_DRR_E_LAUNCH, hipGetErrorString(e));
+    }
+    // (asked of the runtime once per instantiation: at the dynamic LDS of its first launch, which only the masked variants use)
+    static const long long resident = [&] {
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), WG, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 2;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+        return (long long)per_cu * (cus >= 8 ? cus - cus % 8 : cus);   // a multiple of 8 workgroups: xcd_remap keeps an XCD on its own range
+    }();
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks < resident ? nblocks : resident)), dim3(WG), lds_bytes, (hipStream_t)stream, A);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(XVR_DRR_E_LAUNCH, hipGetErrorString(e));
+    return XVR_DRR_OK;
+#endif
+}
 
 }  // namespace
 
@@ -897,7 +928,7 @@ int xvr_drr_trilinear_backward(const float* volume, const float* mask, int D0, i
 #define TRI_BWD_PAIR(M, CL)                                                                   \
         do {                                                                                  \
             if (gpose) { rc = TRI_BWD_ONE(M, CL, true, false, Ap); if (rc) return rc; }       \
-            return TRI_BWD_ONE(M, CL, false, true, Av);                                       \
+            return launch_fallback(k_trilinear_bwd<M, CL, false, true>, Av, lds, stream);     \
         } while (0)
         if (mask) { if (clip) TRI_BWD_PAIR(true, true); else TRI_BWD_PAIR(true, false); }
         if (clip) TRI_BWD_PAIR(false, true); else TRI_BWD_PAIR(false, false);

@@ -19,9 +19,13 @@ from . import _lib
 from .data import Subject
 from .detector import Detector, make_reorient
 from .pose import RigidTransform, convert
-from .renderers import Siddon, Trilinear, _ptr, _stream, _timed, render_from_camera
+from .renderers import PoseTail, Siddon, Trilinear, _ptr, _stream, _timed, render_from_camera
 
 __all__ = ["DRR", "rays_from_camera"]
+
+# DRR.forward from Euler angles with a voxel gradient wanted: the pose side of the backward is ONE launch (renderers.PoseTail).
+# False: the three launches of the autograd chain (backward_from_jac -> rays_backward -> pose_camera_backward), for A/B runs.
+FUSED_POSE_TAIL = True
 
 
 class _RaysFromCamera(torch.autograd.Function):
@@ -130,8 +134,9 @@ class DRR(torch.nn.Module):
             # (xvr_pose_camera_forward), one addmm from a 4x4 pose -- instead of the ~60 tiny torch launches of
             # convert() + camera(), which cost 0.5 ms per call and dominate a one-pose render
             G, c = self._camera_affine_cached()
-            if (parameterization == "euler_angles" and len(args) == 2 and args[0].is_cuda and args[1].is_cuda
-                    and args[0].dtype == args[1].dtype == torch.float32 and args[0].dim() == 2 and len(args[0]) > 0):
+            euler = (parameterization == "euler_angles" and len(args) == 2 and args[0].is_cuda and args[1].is_cuda
+                     and args[0].dtype == args[1].dtype == torch.float32 and args[0].dim() == 2 and len(args[0]) > 0)
+            if euler:
                 from .pose_opt import pose_camera
                 batch_size = len(args[0])
                 cam = pose_camera(args[0], args[1], G, c, convention)
@@ -149,8 +154,19 @@ class DRR(torch.nn.Module):
                 img = render_from_camera(density, cam, self.renderer.make_spec(**kwargs), self.detector.height,
                                          self.detector.width)
             else:
+                tail = None
+                if euler and FUSED_POSE_TAIL and not mask_to_channels and not batch_window and torch.is_grad_enabled() \
+                        and (args[0].requires_grad or args[1].requires_grad):
+                    # (every Euler call that did not take render_from_camera above: a voxel gradient is wanted, or extra renderer
+                    #  keywords, or a detector one pixel wide)  pose parameters -> camera -> rays all on the device: the rays carry
+                    # no autograd history and the backward goes from the render's jacobian to d/d(rot, xyz) in one launch
+                    # (renderers.PoseTail) instead of three
+                    tail = PoseTail(args[0], args[1], cam.detach(), G, self.detector.height, self.detector.width, convention)
+                    cam = cam.detach()
                 source, target, img = rays_from_camera(cam, self.detector.height, self.detector.width)
                 kwargs["mask"] = self.mask if mask_to_channels else None
+                if tail is not None:
+                    kwargs["pose_tail"] = tail
                 img = self.renderer(density, source, target, img, **kwargs)
         else:
             pose = args[0] if parameterization is None else convert(

@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from .spec import RenderSpec
 
-__all__ = ["Siddon", "Trilinear", "render", "render_from_camera", "make_cspec", "invalidate_volume_cache"]
+__all__ = ["Siddon", "Trilinear", "render", "render_from_camera", "make_cspec", "invalidate_volume_cache", "PoseTail"]
 
 
 def make_cspec(shape, spec: RenderSpec, ray_grid_w: int = 0, volume_layout: int = 0) -> _lib.CSpec:
@@ -331,12 +331,52 @@ def _use_ypairs(spec, volume, B, n):
             and elements < 2 ** 31 and min(D0, D1, D2) >= 2 and (D2 < 8192 or not YPAIR_TILES))
 
 
-class _Render(torch.autograd.Function):
-    """forward: one fused sweep (with the per-ray jacobian when a pose gradient may be needed);
-    backward: elementwise-from-jacobian for the pose, a re-march with scatter for the voxels."""
+class PoseTail:
+    """Where the rays of a render came from, when that was the device: pose parameters -> cam [B,24] (xvr_pose_camera_forward /
+    _param) -> rays (xvr_drr_rays_forward).  Handed to ``render`` next to (detached) source / target / img, it lets the backward go
+    from the saved jacobian to d/d(rot, xyz) in ONE launch (xvr_drr_jac_to_pose_backward) instead of jacobian -> per-ray gradients
+    -> camera -> parameters in three.  ``kind`` / ``pose_jac``: xvr_pose_camera_forward_param's (0 / None: Euler angles)."""
+
+    def __init__(self, rot, xyz, cam, G, height, width, convention="ZXY", kind=0, pose_jac=None):
+        self.rot, self.xyz, self.cam, self.G = rot, xyz, cam, G
+        self.H, self.W, self.convention, self.kind, self.pose_jac = int(height), int(width), convention, int(kind), pose_jac
+
+    def tensors(self):
+        """What the backward needs, for ctx.save_for_backward: rot / xyz go through autograd's saved-tensor check, so a caller who
+        steps them in place between forward and backward gets an error, not the chain rule at the new values."""
+        return self.rot, self.xyz, self.cam, self.G, self.pose_jac
+
+    def meta(self):
+        return self.H, self.W, self.convention, self.kind
 
     @staticmethod
-    def forward(ctx, volume, source, target, img, mask, spec: RenderSpec, ray_grid_w: int, C: int, work, hu_map=None):
+    def backward(lib, meta, tensors, jac, gout):
+        """-> (d/d rot, d/d xyz) from the render's jacobian and the upstream gradient [B, n] (one launch, fixed-order sums)."""
+        from .pose_opt import axes_of
+        H, W, convention, kind = meta
+        rot, xyz, cam, G, pose_jac = tensors
+        rot_c, xyz_c, B = rot.detach().contiguous(), xyz.detach().contiguous(), cam.shape[0]
+        g_rot, g_xyz = torch.empty_like(rot_c), torch.empty_like(xyz_c)
+        nbytes = lib.xvr_drr_jac_to_camera_workspace_bytes(B, H, W)
+        key = ("j2c", cam.device, torch.cuda.current_stream(cam.device).cuda_stream)
+        ws = _WORKSPACES.get(key)
+        if ws is None or ws.numel() * 4 < nbytes:   # zero-filled once; every call leaves it ready for the next
+            ws = _WORKSPACES[key] = torch.zeros((nbytes + 3) // 4, device=cam.device, dtype=torch.float32)
+        rc = _timed("jac_to_pose_backward", lib.xvr_drr_jac_to_pose_backward, _ptr(jac), _ptr(gout), _ptr(cam), B, H, W,
+                    _ptr(rot_c), _ptr(xyz_c), kind, axes_of(convention if kind == 0 else "ZXY"), _ptr(G),
+                    _ptr(pose_jac), _ptr(g_rot), _ptr(g_xyz), None, _ptr(ws), ws.numel() * 4, _stream())
+        _lib.check(rc, "xvr_drr_jac_to_pose_backward")
+        return g_rot, g_xyz
+
+
+class _Render(torch.autograd.Function):
+    """forward: one fused sweep (with the per-ray jacobian when a pose gradient may be needed);
+    backward: elementwise-from-jacobian for the pose (straight to the pose parameters with a PoseTail), a re-march with scatter
+    for the voxels."""
+
+    @staticmethod
+    def forward(ctx, volume, source, target, img, mask, spec: RenderSpec, ray_grid_w: int, C: int, work, hu_map=None,
+                tail=None, rot=None, xyz=None):
         lib = _lib.load()
         D0, D1, D2 = volume.shape
         B, n, _ = target.shape
@@ -345,8 +385,9 @@ class _Render(torch.autograd.Function):
         tgt_c = target.contiguous()
         len_c = img.reshape(B, n).contiguous()
         msk_c = mask.contiguous() if mask is not None else None
-        need_pose = any(ctx.needs_input_grad[1:4])
+        need_pose = any(ctx.needs_input_grad[1:4]) or (tail is not None and any(ctx.needs_input_grad[11:13]))
         use_jac = need_pose  # with a mask: the jacobian of the channel sum (see backward)
+        ctx.tail = tail.meta() if tail is not None else None
         out = torch.empty(B, C, n, device=volume.device, dtype=torch.float32)
         jac = torch.empty(B, n, _lib.JAC_STRIDE, device=volume.device, dtype=torch.float32) if use_jac else None
         fn = lib.xvr_drr_trilinear_forward if spec.renderer == "trilinear" else lib.xvr_drr_siddon_forward
@@ -385,13 +426,13 @@ class _Render(torch.autograd.Function):
         ctx.spec, ctx.ray_grid_w, ctx.C = spec, ray_grid_w, C
         ctx.src_shape, ctx.img_shape = source.shape, img.shape
         ctx.window, ctx.hu_map = window, hu_map
-        ctx.save_for_backward(vol_c, src_c, tgt_c, len_c, msk_c, jac)
+        ctx.save_for_backward(vol_c, src_c, tgt_c, len_c, msk_c, jac, *(tail.tensors() if tail is not None else ()))
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lib = _lib.load()
-        vol_c, src_c, tgt_c, len_c, msk_c, jac = ctx.saved_tensors
+        vol_c, src_c, tgt_c, len_c, msk_c, jac = ctx.saved_tensors[:6]
         spec, C = ctx.spec, ctx.C
         D0, D1, D2 = vol_c.shape
         B, n, _ = tgt_c.shape
@@ -407,6 +448,12 @@ class _Render(torch.autograd.Function):
         need_pose = any(ctx.needs_input_grad[1:4])
         gvol = torch.zeros_like(vol_c) if need_vol else None
         gsrc = gtgt = glen = None
+        g_rot = g_xyz = None
+        if ctx.tail is not None and any(ctx.needs_input_grad[11:13]):
+            # rays generated on the device from the pose parameters (one channel, no alpha window: render() refuses a tail
+            # otherwise): jacobian -> parameters in one launch, issued BEFORE the voxel gradient's launches, which it does not
+            # depend on -- nothing of the pose side is left behind the splat
+            g_rot, g_xyz = PoseTail.backward(lib, ctx.tail, ctx.saved_tensors[6:], jac, g_uniform)
         if need_pose:
             gsrc = torch.zeros(B, 3, device=dev, dtype=torch.float32)
             gtgt = torch.empty(B, n, 3, device=dev, dtype=torch.float32)
@@ -479,7 +526,8 @@ class _Render(torch.autograd.Function):
         g_source = gsrc.reshape(ctx.src_shape) if need_pose and ctx.needs_input_grad[1] else None
         g_target = gtgt if need_pose and ctx.needs_input_grad[2] else None
         g_img = glen.reshape(ctx.img_shape) if need_pose and ctx.needs_input_grad[3] else None
-        return gvol, g_source, g_target, g_img, None, None, None, None, None, None
+        return (gvol, g_source, g_target, g_img, None, None, None, None, None, None, None,
+                g_rot if ctx.needs_input_grad[11] else None, g_xyz if ctx.needs_input_grad[12] else None)
 
 
 class _RenderFromCamera(torch.autograd.Function):
@@ -540,9 +588,10 @@ def render_from_camera(volume, cam, spec: RenderSpec, height: int, width: int):
     return _RenderFromCamera.apply(cam, volume, spec, int(height), int(width))
 
 
-def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w: int = 0, n_channels=None, work=None):
+def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w: int = 0, n_channels=None, work=None, pose_tail=None):
     """Functional form.  ``work``: optional cuda uint64/int64 scalar the kernel adds its count of
-    volume-touching samples (trilinear) or voxel segments (siddon) to."""
+    volume-touching samples (trilinear) or voxel segments (siddon) to.  ``pose_tail``: a PoseTail -- source / target / img were
+    generated on the device from its pose parameters and carry no autograd history; the pose gradient goes to the parameters."""
     hu_map = None
     if type(volume).__name__ == "HUDensity":   # (xvr_amd.data.HUDensity: a density that has not been written yet)
         volume.check_fresh()
@@ -576,7 +625,12 @@ def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w:
         # label-carrying y-pair copy, with nothing to differentiate w.r.t. the voxels; everything else gets the density written
         if not (mask is not None and _packed_tiles_ok(spec, volume, mask, B, n, C) and YPAIR_TILES and YPAIR_TILES_PACKED):
             hu_map, volume = None, hu_map.materialize()
-    return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map)
+    if pose_tail is None:
+        return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, None, None, None)
+    if mask is not None or spec.clip_to_volume == "batch" or source.requires_grad or target.requires_grad or img.requires_grad \
+            or pose_tail.H * pose_tail.W != n or pose_tail.cam.shape[0] != B:
+        raise ValueError("pose_tail: one channel, no batch alpha window, rays of the tail's own [B, H * W] detector without autograd history")
+    return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, pose_tail, pose_tail.rot, pose_tail.xyz)
 
 
 def _packed_tiles_ok(spec, volume, mask, B, n, C) -> bool:
@@ -637,9 +691,9 @@ class Trilinear(_RendererBase):
     def make_spec(self, n_points: int = 500, align_corners: bool = False) -> RenderSpec:
         return self._spec(near=self.near, far=self.far, n_points=n_points, align_corners=align_corners)
 
-    def forward(self, volume, source, target, img, n_points: int = 500, align_corners: bool = False, mask=None):
+    def forward(self, volume, source, target, img, n_points: int = 500, align_corners: bool = False, mask=None, pose_tail=None):
         spec = self.make_spec(n_points, align_corners)
-        return render(volume, source, target, img, spec, mask, self._grid_w(target.shape[1]), self._n_channels(mask))
+        return render(volume, source, target, img, spec, mask, self._grid_w(target.shape[1]), self._n_channels(mask), pose_tail=pose_tail)
 
 
 class Siddon(_RendererBase):
@@ -659,8 +713,8 @@ class Siddon(_RendererBase):
     def make_spec(self, align_corners: bool = False) -> RenderSpec:
         return self._spec(align_corners=align_corners)
 
-    def forward(self, volume, source, target, img, align_corners: bool = False, mask=None):
+    def forward(self, volume, source, target, img, align_corners: bool = False, mask=None, pose_tail=None):
         spec = self.make_spec(align_corners)
         if self.stop_gradients_through_grid_sample:
             volume = volume.detach()
-        return render(volume, source, target, img, spec, mask, self._grid_w(target.shape[1]), self._n_channels(mask))
+        return render(volume, source, target, img, spec, mask, self._grid_w(target.shape[1]), self._n_channels(mask), pose_tail=pose_tail)
