@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define XVR_DRR_ABI_VERSION 12   /* (xvr_drr_jac_to_pose_backward was ADDED under 12: no existing entry point changed shape) 12: xvr_drr_trilinear_backward / xvr_drr_siddon_backward take slab_index, slab_count (an argument of the call where a process-wide option used to carry it); 11: xvr_sim_augment_* (the training step's X-ray augmentations); 10: xvr_sim_ncc_registration_step (the tail of a registration iteration in the similarity's launches); 9: xvr_drr_pack_hu_labels_ytiles, options siddon_splat / gather_splat = 3 / siddon_slab = 2, pose kind 6 (rotation_10d), non-exact Siddon index maps on the slab march and the brick splat, guard-banded fixed point; 8: volume_layout 3 + xvr_drr_pack_ytiles / _labels_ytiles (tiled y-pair copy), xvr_pose_camera_forward_param / xvr_pose_opt_step_param (device-resident registration for every parameterisation; xvr_pose_opt_state holds 13 parameters), xvr_sim_equalize_* write / take the normalised output, options tile_geom, siddon_slab, siddon_gather_fast; 7: xvr_drr_foreground, xvr_drr_pack_labels_ypairs, xvr_sim_dice_bool, xvr_sim_transform_* (xvr_sim.h), xvr_pose_convert_* (xvr_pose.h); 6: xvr_drr_spec.alpha_window + xvr_drr_alpha_window (clip_to_volume = 2); 5: xvr_drr_set_option / xvr_drr_get_option (the A/B switches are no longer getenv calls per launch); 4: volume_layout 2 + xvr_drr_pack_bricks (siddon forward); 3: xvr_drr_spec.volume_layout + xvr_drr_pack_ypairs; 2: xvr_sim_spec grew, camera-driven forwards, packed labels, xvr_pose.h */
+#define XVR_DRR_ABI_VERSION 12   /* (xvr_drr_jac_to_pose_backward, and volume_layout 4 with xvr_drr_htiles_bytes / xvr_drr_pack_htiles -- the tiled y-pair copy in IEEE halves -- were ADDED under 12: no existing entry point changed shape; tests/test_augment.py pins the number, and the binding refuses a library that lacks an export by name) 12: xvr_drr_trilinear_backward / xvr_drr_siddon_backward take slab_index, slab_count (an argument of the call where a process-wide option used to carry it); 11: xvr_sim_augment_* (the training step's X-ray augmentations); 10: xvr_sim_ncc_registration_step (the tail of a registration iteration in the similarity's launches); 9: xvr_drr_pack_hu_labels_ytiles, options siddon_splat / gather_splat = 3 / siddon_slab = 2, pose kind 6 (rotation_10d), non-exact Siddon index maps on the slab march and the brick splat, guard-banded fixed point; 8: volume_layout 3 + xvr_drr_pack_ytiles / _labels_ytiles (tiled y-pair copy), xvr_pose_camera_forward_param / xvr_pose_opt_step_param (device-resident registration for every parameterisation; xvr_pose_opt_state holds 13 parameters), xvr_sim_equalize_* write / take the normalised output, options tile_geom, siddon_slab, siddon_gather_fast; 7: xvr_drr_foreground, xvr_drr_pack_labels_ypairs, xvr_sim_dice_bool, xvr_sim_transform_* (xvr_sim.h), xvr_pose_convert_* (xvr_pose.h); 6: xvr_drr_spec.alpha_window + xvr_drr_alpha_window (clip_to_volume = 2); 5: xvr_drr_set_option / xvr_drr_get_option (the A/B switches are no longer getenv calls per launch); 4: volume_layout 2 + xvr_drr_pack_bricks (siddon forward); 3: xvr_drr_spec.volume_layout + xvr_drr_pack_ypairs; 2: xvr_sim_spec grew, camera-driven forwards, packed labels, xvr_pose.h */
 
 #define XVR_DRR_OK 0
 #define XVR_DRR_E_ARG (-1)     /* bad argument (null pointer, non-positive size, unsupported combo) */
@@ -66,7 +66,8 @@ typedef struct xvr_drr_spec {
     int32_t volume_layout; /* forward only: 0 = `volume` is [D0][D1][D2]; 1 (trilinear) = it is the y-pair interleaved
                               copy written by xvr_drr_pack_ypairs; 2 (siddon) = the 2 x 2 x 8 bricks written by
                               xvr_drr_pack_bricks; 3 (trilinear) = the y-pair copy in 2 x 8 tiles written by
-                              xvr_drr_pack_ytiles (same results, bit for bit)                               */
+                              xvr_drr_pack_ytiles (same results, bit for bit); 4 (trilinear, one channel) = that tiled copy
+                              in IEEE halves, written by xvr_drr_pack_htiles: the render of the volume ROUNDED to half      */
     const float* alpha_window; /* clip_to_volume == 2: device buffer of xvr_drr_alpha_window_bytes(B) bytes, 16-byte aligned, written by
                               xvr_drr_alpha_window() on the same stream before the render (the kernels read the call's
                               near / far / scale from it: no host round trip); NULL otherwise                  */
@@ -304,6 +305,30 @@ int xvr_drr_pack_labels_ytiles(const float* volume, const float* mask, int D0, i
  * volume in between -- the per-step 512 MiB round trip of /root/reference/src/xvr/model/trainer.py:196-197 (round 5). */
 int xvr_drr_pack_hu_labels_ytiles(const float* hu, const float* mask, const void* stats, float bone_multiplier, int D0, int D1, int D2,
                                   float* tiles, void* stream);
+
+/*
+ * The tiled y-pair copy in IEEE halves, volume_layout = 4 (trilinear forward, one channel, both the plain and the ray-generating
+ * entry point, with or without the jacobian, every clip_to_volume setting): an opt-in accuracy trade for a forward that is bound
+ * by fabric bandwidth -- twice the voxels per 128-byte line.
+ *   entry   (half V[x][yp - 1][z], half V[x][yp][z]), 4 bytes, yp = 0 .. D1, zero outside the volume; one 8-byte load at
+ *           (x, floor(y) + 1, z) returns the taps (y, z), (y + 1, z), (y, z + 1), (y + 1, z + 1)
+ *   line    128 bytes = 2 x-rows x 16 z-entries; tiles OVERLAP by one entry along z: tile b holds z = 15 b .. 15 b + 15
+ *   shape   [ceil(D0 / 2)][D1 + 1][(D2 - 2) / 15 + 1][2][16][2] halves = xvr_drr_htiles_bytes(); entry (x, yp, z) is 4-byte word
+ *           ((((x / 2) (D1 + 1) + yp) nbz + z / 15) 32 + (x % 2) 16 + z % 15), nbz = (D2 - 2) / 15 + 1 -- and, for z % 15 == 0, z > 0,
+ *           also word 15 of the tile before; low half = y-row yp - 1, high half = y-row yp
+ *           (the alternative line of 2 x * 2 yp * 8 z entries was not measured against this one and is not built)
+ *   pack    one streaming pass, the ONLY place precision is lost: values are clamped to +-65504 (infinities too) and rounded to
+ *           nearest-even, subnormal halves kept; NaN stays NaN.  The kernels widen the halves exactly and run the fp32 march:
+ *           a render from these tiles of V is, bit for bit (image and jacobian), the volume_layout = 3 render of
+ *           V.clamp(-65504, 65504).half().float().
+ *   D2      at most XVR_DRR_HTILES_MAX_D2: the march's z / 15 is (z * 34953) >> 19, exact for z < 74898 (and the product stays below
+ *           2^32 for z < 122879); longer volumes, and copies of >= 2^31 entries, are refused with XVR_DRR_E_UNSUPPORTED by the pack
+ *           and by the forward.  A forward with volume_layout = 4 marches these tiles at EVERY launch size (the whole-ray kernel):
+ *           it never falls back to an fp32 volume.  Masks / packed labels (C > 1) are refused: the label bits ride in fp32 mantissas.
+ */
+#define XVR_DRR_HTILES_MAX_D2 65535
+size_t xvr_drr_htiles_bytes(int D0, int D1, int D2);
+int xvr_drr_pack_htiles(const float* volume, int D0, int D1, int D2, void* tiles, void* stream);
 
 /*
  * Bricked copy of a volume for the Siddon forward (spec.volume_layout = 2):

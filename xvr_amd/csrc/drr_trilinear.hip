@@ -114,11 +114,11 @@ __device__ __forceinline__ void tri_march(const RenderArgs& A, const Ray& R, con
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if (YP) {
-                // y-pair interleaved copy: two 16-byte loads instead of four 8-byte ones; re-filed as the four (z, z + 1)
+                // y-pair interleaved copy: two 16-byte loads (YP = 3, half tiles: two 8-byte loads) instead of four 8-byte ones; re-filed as the four (z, z + 1)
                 // pairs of rows (x0,y0) (x0,y1) (x1,y0) (x1,y1), so that everything below is the same arithmetic
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const fquad Q = load_quad(vol + yoff[h][q]);
+                    const fquad Q = YP == 3 ? load_hquad(vol + yoff[h][q]) : load_quad(vol + yoff[h][q]);
                     P[h][2 * q] = fpair{Q.x, Q.z};
                     P[h][2 * q + 1] = fpair{Q.y, Q.w};
                 }
@@ -775,7 +775,12 @@ static int trilinear_forward_impl(const float* volume, const float* mask, int D0
     if (packed && C > (1 << LABEL_BITS)) return fail(XVR_DRR_E_ARG, "packed labels hold at most 16 channels");
     if (sp->alpha_window && jac && (mask || packed))
         return fail(XVR_DRR_E_UNSUPPORTED, "clip_to_volume == 2: the jacobian is implemented for one channel");
-    if (sp->volume_layout != 0 && sp->volume_layout != 1 && sp->volume_layout != 3) return fail(XVR_DRR_E_ARG, "unknown volume_layout");
+    if (sp->volume_layout != 0 && sp->volume_layout != 1 && sp->volume_layout != 3 && sp->volume_layout != 4)
+        return fail(XVR_DRR_E_ARG, "unknown volume_layout");
+    const bool htiles = sp->volume_layout == 4;   // the tiled y-pair copy in IEEE halves (xvr_drr_pack_htiles)
+    if (htiles && (mask || C > 1)) return fail(XVR_DRR_E_UNSUPPORTED, "the half tiles render one channel (labels ride in fp32 mantissa bits)");
+    if (htiles && ((long long)((D0 + 1) / 2) * (D1 + 1) * ((D2 - 2) / 15 + 1) * 32 >= (1LL << 31) || D2 > HTILE_MAX_D2))
+        return fail(XVR_DRR_E_UNSUPPORTED, "half tiles: D2 beyond XVR_DRR_HTILES_MAX_D2, or a copy of >= 2^31 entries");
     const bool ypl = sp->volume_layout == 1 || sp->volume_layout == 3;   // a y-pair copy: rows (1) or 2 x 8 tiles (3)
     if (ypl && mask) return fail(XVR_DRR_E_UNSUPPORTED, "the y-pair layouts take labels packed into the volume, not a mask volume");
     if (sp->volume_layout == 1 && (long long)D0 * (D1 + 1) * D2 * 2 >= (1LL << 31))
@@ -816,7 +821,8 @@ static int trilinear_forward_impl(const float* volume, const float* mask, int D0
         RenderArgs Aw = A;
         return sp->volume_layout == 1 ? launch(k_trilinear_fwd<true, 0, false, 1, true>, Aw, 0, stream)
                                       : (sp->volume_layout == 3 ? launch(k_trilinear_fwd<true, 0, false, 2, true>, Aw, 0, stream)
-                                                                : launch(k_trilinear_fwd<true, 0, false, 0, true>, Aw, 0, stream));
+                                         : (htiles ? launch(k_trilinear_fwd<true, 0, false, 3, true>, Aw, 0, stream)
+                                                   : launch(k_trilinear_fwd<true, 0, false, 0, true>, Aw, 0, stream)));
     }
     // Large batches over a volume the Infinity Cache cannot hold: the slab-major march (k_trilinear_fwd_slab).  Option
     // "fwd_slabs": 0 = never, n >= 2 = always n slabs, -1 (default) = as many slabs as keep a slab's bytes under
@@ -830,7 +836,7 @@ static int trilinear_forward_impl(const float* volume, const float* mask, int D0
         const int axis = xvr_detail::option(xvr_detail::OPT_FWD_SLAB_AXIS);
         const int Daxis = axis == 0 ? D0 : (axis == 1 ? D1 : D2);
         if (nslabs > Daxis / 4) nslabs = Daxis / 4;
-        if (nslabs >= 2 && !clip && A.grid_w > 0 && sp->volume_layout != 3) {
+        if (nslabs >= 2 && !clip && A.grid_w > 0 && sp->volume_layout != 3 && !htiles) {
             for (int s = 0; s < nslabs; ++s) {
                 SlabRange S;
                 S.axis = axis;
@@ -852,6 +858,9 @@ static int trilinear_forward_impl(const float* volume, const float* mask, int D0
     }
     if (sp->volume_layout == 1) XVR_YP_LAUNCH(0, 1, 0);   // `volume` is a y-pair copy: the unsplit kernel, whatever the launch size
     if (sp->volume_layout == 3) XVR_YP_LAUNCH(0, 2, 0);
+    // half tiles: the whole-ray kernel at EVERY launch size -- the sample-split kernels march the natural fp32 layout, and a render
+    // must be the same function of the rounded volume whatever its size
+    if (htiles) XVR_YP_LAUNCH(0, 3, 0);
 #undef XVR_YP_LAUNCH
     bool tile16 = false;
     const int ns = split_factor(B, n, (long long)D0 * D1 * D2, false, &tile16);

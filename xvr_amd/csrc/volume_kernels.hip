@@ -234,6 +234,38 @@ __global__ __launch_bounds__(TB) void k_pack_ytiles(const float* __restrict__ vo
     }
 }
 
+// htiles[x / 2][yp][z / 15][x % 2][z - 15 (z / 15) in 0..15] = (half V[x][yp - 1][z], half V[x][yp][z]): k_pack_ytiles' layout with IEEE-half
+// entries (volume_layout 4) -- a 128-byte line holds 2 x-rows x 16 z-entries, tile b holds z = 15 b .. 15 b + 15 (one entry of overlap,
+// so that the 8 bytes of any (z, z + 1) pair lie inside one tile).  One thread per 16 bytes = four z-entries of one tile row.
+// The ONLY place where precision is lost: non-NaN values are clamped to +-65504 (the largest finite half) and rounded to nearest-even;
+// NaN stays NaN.  Half subnormals are kept (1e-6 -> 17 x 2^-24).
+__device__ __forceinline__ unsigned short to_half_bits(const float v) {
+    const float c = v != v ? v : fminf(fmaxf(v, -65504.f), 65504.f);
+    return __builtin_bit_cast(unsigned short, (_Float16)c);   // v_cvt_f16_f32: round to nearest-even
+}
+__global__ __launch_bounds__(TB) void k_pack_htiles(const float* __restrict__ vol, int D0, int D1, int D2, uint4* __restrict__ tiles) {
+    const int nbx = (D0 + 1) >> 1, nbz = (D2 - 2) / 15 + 1;
+    const long long total = (long long)nbx * (D1 + 1) * nbz * 8;
+    for (long long t = (long long)blockIdx.x * TB + threadIdx.x; t < total; t += (long long)gridDim.x * TB) {
+        const int piece = (int)(t & 7), xr = piece >> 2, quarter = piece & 3;
+        const long long tile = t >> 3;
+        const int bz = (int)(tile % nbz);
+        const long long row = tile / nbz;
+        const int yp = (int)(row % (D1 + 1)), x = (int)(row / (D1 + 1)) * 2 + xr;
+        unsigned e[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int z = 15 * bz + 4 * quarter + r;
+            const bool in = x < D0 && z < D2;
+            const long long olo = ((long long)x * D1 + (yp - 1)) * D2 + z, ohi = ((long long)x * D1 + yp) * D2 + z;
+            const unsigned lo = in && yp >= 1 ? to_half_bits(vol[olo]) : 0u;
+            const unsigned hi = in && yp <= D1 - 1 ? to_half_bits(vol[ohi]) : 0u;
+            e[r] = lo | (hi << 16);
+        }
+        tiles[t] = make_uint4(e[0], e[1], e[2], e[3]);
+    }
+}
+
 // bricks[x / 2][y / 2][z / 8][x % 2][y % 2][z % 8]: one 128-byte line = a 2 x 2 x 8 block of voxels (zeros beyond the volume);
 // one thread per 4 z of one (x, y) = one 16-byte load (where aligned) and one 16-byte store
 __global__ __launch_bounds__(TB) void k_pack_bricks(const float* __restrict__ vol, int D0, int D1, int D2, float* __restrict__ bricks) {
@@ -343,6 +375,25 @@ int xvr_drr_pack_hu_labels_ytiles(const float* hu, const float* mask, const void
                                   float* tiles, void* stream_) {
     if (!mask || !stats) return vfail(XVR_DRR_E_ARG, "bad argument");
     return pack_ytiles_impl(hu, mask, D0, D1, D2, tiles, stream_, stats, bone_multiplier);
+}
+
+size_t xvr_drr_htiles_bytes(int D0, int D1, int D2) {
+    if (D0 <= 0 || D1 <= 0 || D2 < 2) return 0;
+    return (size_t)((D0 + 1) / 2) * (size_t)(D1 + 1) * (size_t)((D2 - 2) / 15 + 1) * 128;
+}
+
+int xvr_drr_pack_htiles(const float* volume, int D0, int D1, int D2, void* tiles, void* stream_) {
+    if (!volume || !tiles || D0 < 2 || D1 < 2 || D2 < 2) return vfail(XVR_DRR_E_ARG, "bad argument");
+    if (reinterpret_cast<uintptr_t>(tiles) & 15u) return vfail(XVR_DRR_E_ARG, "the tiled copy must be 16-byte aligned");
+    if (D2 > XVR_DRR_HTILES_MAX_D2)
+        return vfail(XVR_DRR_E_UNSUPPORTED, "half tiles: D2 beyond XVR_DRR_HTILES_MAX_D2 (the march's z / 15 is a multiply-shift)");
+    const long long total = (long long)((D0 + 1) / 2) * (D1 + 1) * ((D2 - 2) / 15 + 1) * 8;   // 16-byte pieces of four entries
+    if (total * 4 >= (1LL << 31)) return vfail(XVR_DRR_E_UNSUPPORTED, "half-tile copy has >= 2^31 entries");
+    const long long blocks = (total + TB - 1) / TB;
+    hipLaunchKernelGGL(k_pack_htiles, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(TB), 0, (hipStream_t)stream_, volume, D0, D1, D2,
+                       static_cast<uint4*>(tiles));
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? XVR_DRR_OK : vfail(XVR_DRR_E_LAUNCH, hipGetErrorString(e));
 }
 
 int xvr_drr_pack_labels(const float* volume, const float* mask, long long n, float* packed, void* stream_) {

@@ -129,6 +129,10 @@ class DRR(torch.nn.Module):
         """``drr(pose)`` with a RigidTransform, or ``drr(rot, xyz, parameterization=, convention=)``.
         ``density`` overrides the module's buffer (e.g. a leaf tensor whose gradient is wanted)."""
         density = self.density if density is None else density
+        storage = getattr(self.renderer, "volume_storage", "float32")
+        if storage == "float16" and mask_to_channels:
+            raise NotImplementedError("volume_storage='float16': mask_to_channels renders carry their labels in float32 mantissa bits; "
+                                      "render them from a float32-storage module")
         if self.fused_rays and calibration is None and density.is_cuda:
             # pose -> camera through the affine map of camera_affine(): ONE HIP launch from Euler angles
             # (xvr_pose_camera_forward), one addmm from a 4x4 pose -- instead of the ~60 tiny torch launches of
@@ -152,7 +156,7 @@ class DRR(torch.nn.Module):
                 # pose gradient only, one channel (the registration loop): the render kernel generates the rays
                 # itself and the backward is one fixed-order kernel -- no [B, n, 3] targets in between
                 img = render_from_camera(density, cam, self.renderer.make_spec(**kwargs), self.detector.height,
-                                         self.detector.width)
+                                         self.detector.width, volume_storage=storage)
             else:
                 tail = None
                 if euler and FUSED_POSE_TAIL and not mask_to_channels and not batch_window and torch.is_grad_enabled() \

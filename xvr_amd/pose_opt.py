@@ -151,7 +151,10 @@ class RegistrationStage:
         if self._vol_version == (vol.data_ptr(), vol._version):
             return
         pairs, layout = None, 0
-        if R._use_ypairs(self.rspec, vol, self.B, self.n):
+        if getattr(self.drr.renderer, "volume_storage", "float32") == "float16":   # the module's half tiles, whatever the launch size
+            R._refuse_for_half(vol, None, None)
+            pairs, layout = R._half_volume(self.lib, vol), 4
+        elif R._use_ypairs(self.rspec, vol, self.B, self.n):
             pairs, layout = R._layout_copy(self.lib, vol, "ypairs", first_sight=True), (3 if R.YPAIR_TILES else 1)
         elif R._use_bricks(self.rspec, vol, self.B, self.n):
             pairs, layout = R._brick_volume(self.lib, vol), 2

@@ -235,7 +235,7 @@ BRICK_LAYOUT = _os.environ.get("XVR_DRR_BRICKS", "1") != "0"
 # renders of a volume version BEFORE its copy is built (measured with the volume changing every step, bench.py --update-volume:
 # the y-pair copy costs 0.54 ms and saves 0.70 of the forward -- 14.75 -> 14.96 ms per step with the splat behind it, no gain --;
 # the bricked copy saves 1.3 ms of the Siddon walk: 21.46 -> 20.51 ms per step when built at first sight)
-LAYOUT_COPY_AFTER = {"ypairs": 2, "bricks": 0}
+LAYOUT_COPY_AFTER = {"ypairs": 2, "bricks": 0, "htiles": 0}
 # Round 6: on the TILED y-pair copy (round 4) the forward of a large launch is 1.7 ms faster than on the natural layout (C2:
 # 4.76 against 6.48 ms, profiles/r06_trilinear_rocprof_summary.md) and the copy costs 0.6 ms -- the measurement above is of round
 # 2's row layout.  A launch whose saving (~0.45 ms per 1e9 nominal samples) exceeds the copy's cost (0.6 ms per 512^3 voxels) builds
@@ -262,7 +262,9 @@ def _layout_copy(lib, volume, kind, first_sight=False):
     if seen <= LAYOUT_COPY_AFTER[kind] and not first_sight:
         slot[kind] = (key, None, buf, seen)
         return None
-    if kind == "ypairs":
+    if kind == "htiles":
+        nbytes, pack, name = lib.xvr_drr_htiles_bytes, lib.xvr_drr_pack_htiles, "pack_htiles"
+    elif kind == "ypairs":
         nbytes, pack, name = ((lib.xvr_drr_ytiles_bytes, lib.xvr_drr_pack_ytiles, "pack_ypairs") if YPAIR_TILES
                               else (lib.xvr_drr_ypairs_bytes, lib.xvr_drr_pack_ypairs, "pack_ypairs"))
     else:
@@ -282,6 +284,43 @@ def _ypair_volume(lib, volume, samples=0):
     (B n n_points): a launch large enough to pay for the tiled copy gets it at first sight (YPAIR_FIRST_SIGHT_SAMPLES_PER_VOXEL)."""
     first = YPAIR_TILES and samples > YPAIR_FIRST_SIGHT_SAMPLES_PER_VOXEL * volume.numel()
     return _layout_copy(lib, volume, "ypairs", first), (3 if YPAIR_TILES else 1)
+
+
+# ``volume_storage="float16"`` (Trilinear): every forward marches the tiled y-pair copy in IEEE halves (xvr_drr_pack_htiles,
+# volume_layout 4) -- the render of the volume rounded to half, an opt-in accuracy trade (DESIGN.md section 4.6).  The copy is a
+# third kind in the cache above, built at first sight (the user asked for it) and rebuilt when the tensor's version changes.
+VOLUME_STORAGES = ("float32", "float16")
+HTILES_MAX_D2 = 65535          # XVR_DRR_HTILES_MAX_D2
+
+
+def check_volume_storage(volume_storage, renderer="trilinear"):
+    if volume_storage not in VOLUME_STORAGES:
+        raise ValueError(f"volume_storage must be one of {VOLUME_STORAGES}, got {volume_storage!r}")
+    if volume_storage == "float16" and renderer != "trilinear":
+        raise ValueError("volume_storage='float16' is a layout of the trilinear forward; Siddon renders the float32 volume")
+    return volume_storage
+
+
+def _half_volume(lib, volume):
+    """The half-tile copy of ``volume`` (a contiguous float32 [D0, D1, D2] tensor): the ONLY thing a float16-storage render reads."""
+    D0, D1, D2 = volume.shape
+    if min(D0, D1, D2) < 2 or D2 > HTILES_MAX_D2 or ((D0 + 1) // 2) * (D1 + 1) * ((D2 - 2) // 15 + 1) * 32 >= 2 ** 31:
+        raise ValueError(f"volume_storage='float16': a volume of shape {(D0, D1, D2)} is outside the half tiles' range "
+                         f"(every axis >= 2, the last at most {HTILES_MAX_D2}, fewer than 2^31 tile entries)")
+    return _layout_copy(lib, volume, "htiles", first_sight=True)
+
+
+def _refuse_for_half(volume, mask, hu_map):
+    """What float16 storage does not render raises -- never a picture from the float32 volume instead."""
+    if hu_map is not None:
+        raise NotImplementedError("volume_storage='float16': a lazy HU density (transform_hu_to_density(..., lazy=True)) is packed "
+                                  "with its labels in float32; materialize() it first")
+    if mask is not None:
+        raise NotImplementedError("volume_storage='float16': mask / mask_to_channels renders carry their labels in float32 mantissa "
+                                  "bits; render them from a float32-storage module")
+    if volume.requires_grad:
+        raise NotImplementedError("volume_storage='float16': no voxel gradient through the rounded copy; detach the density, or use "
+                                  "float32 storage")
 
 
 def _brick_volume(lib, volume):
@@ -376,7 +415,7 @@ class _Render(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, volume, source, target, img, mask, spec: RenderSpec, ray_grid_w: int, C: int, work, hu_map=None,
-                tail=None, rot=None, xyz=None):
+                tail=None, rot=None, xyz=None, volume_storage="float32"):
         lib = _lib.load()
         D0, D1, D2 = volume.shape
         B, n, _ = target.shape
@@ -393,14 +432,17 @@ class _Render(torch.autograd.Function):
         fn = lib.xvr_drr_trilinear_forward if spec.renderer == "trilinear" else lib.xvr_drr_siddon_forward
         vol_f, msk_f = vol_c, msk_c
         pairs, pairs_layout = None, 1
-        if msk_c is not None and PACK_LABELS and 2 <= C <= 16 and vol_c.data_ptr() % 16 == 0 and msk_c.data_ptr() % 16 == 0:
+        half = volume_storage == "float16"
+        if half:    # (render() has refused masks, lazy HU densities and voxel gradients)
+            pairs, pairs_layout = _half_volume(lib, vol_c), 4
+        elif msk_c is not None and PACK_LABELS and 2 <= C <= 16 and vol_c.data_ptr() % 16 == 0 and msk_c.data_ptr() % 16 == 0:
             if _use_ypairs(spec, vol_c, B, n):
                 (pairs, pairs_layout), msk_f = _packed_ypair_volume(lib, vol_c, msk_c, hu_map), None   # labels in the taps AND the y-pair layout, one pass
             else:
                 vol_f, msk_f = _packed_volume(lib, vol_c, msk_c), None     # labels ride in the taps
         if pairs is None and msk_f is None and _use_ypairs(spec, vol_c, B, n):
             pairs, pairs_layout = _ypair_volume(lib, vol_f, B * n * spec.n_points)
-        bricks = _brick_volume(lib, vol_f) if msk_f is None and _use_bricks(spec, vol_c, B, n, C) else None
+        bricks = _brick_volume(lib, vol_f) if msk_f is None and not half and _use_bricks(spec, vol_c, B, n, C) else None
         if pairs is not None:
             vol_f = pairs                                              # (of the label-carrying copy when there is one)
         if bricks is not None:
@@ -527,7 +569,7 @@ class _Render(torch.autograd.Function):
         g_target = gtgt if need_pose and ctx.needs_input_grad[2] else None
         g_img = glen.reshape(ctx.img_shape) if need_pose and ctx.needs_input_grad[3] else None
         return (gvol, g_source, g_target, g_img, None, None, None, None, None, None, None,
-                g_rot if ctx.needs_input_grad[11] else None, g_xyz if ctx.needs_input_grad[12] else None)
+                g_rot if ctx.needs_input_grad[11] else None, g_xyz if ctx.needs_input_grad[12] else None, None)
 
 
 class _RenderFromCamera(torch.autograd.Function):
@@ -536,11 +578,15 @@ class _RenderFromCamera(torch.autograd.Function):
     one channel: what the reference's registration loop differentiates."""
 
     @staticmethod
-    def forward(ctx, cam, volume, spec: RenderSpec, H: int, W: int):
+    def forward(ctx, cam, volume, spec: RenderSpec, H: int, W: int, volume_storage="float32"):
         lib = _lib.load()
         cam_c, vol_c = cam.contiguous(), volume.contiguous()
         B, n = cam_c.shape[0], H * W
-        pairs, layout = _ypair_volume(lib, vol_c, B * n * spec.n_points) if _use_ypairs(spec, vol_c, B, n) else (None, 0)
+        half = volume_storage == "float16"
+        if half:
+            pairs, layout = _half_volume(lib, vol_c), 4
+        else:
+            pairs, layout = _ypair_volume(lib, vol_c, B * n * spec.n_points) if _use_ypairs(spec, vol_c, B, n) else (None, 0)
         if pairs is None and _use_bricks(spec, vol_c, B, n):
             pairs, layout = _brick_volume(lib, vol_c), 2               # (siddon: the bricked copy takes the same seat)
         if pairs is None:
@@ -573,26 +619,35 @@ class _RenderFromCamera(torch.autograd.Function):
         rc = _timed("jac_to_camera_backward", lib.xvr_drr_jac_to_camera_backward, _ptr(jac), _ptr(gout.contiguous()), _ptr(cam_c),
                     B, H, W, _ptr(g_cam), _ptr(ws), ws.numel() * 4, _stream())
         _lib.check(rc, "xvr_drr_jac_to_camera_backward")
-        return g_cam, None, None, None, None
+        return g_cam, None, None, None, None, None
 
 
-def render_from_camera(volume, cam, spec: RenderSpec, height: int, width: int):
+def render_from_camera(volume, cam, spec: RenderSpec, height: int, width: int, volume_storage: str = "float32"):
     """One-channel render straight from the camera vector of ``DRR.camera`` / ``pose_camera`` ([B,24]); the
-    volume is treated as a constant (no voxel gradient on this path)."""
+    volume is treated as a constant (no voxel gradient on this path).  ``volume_storage``: as ``render``."""
+    check_volume_storage(volume_storage, spec.renderer)
+    if volume_storage == "float16":
+        _refuse_for_half(volume, None, volume if type(volume).__name__ == "HUDensity" else None)
     _check_gpu_f32("volume", volume)
     _check_gpu_f32("cam", cam)
     if volume.dim() != 3 or cam.dim() != 2 or cam.shape[1] != 24:
         raise ValueError("volume must be [D0, D1, D2] and cam [B, 24]")
     if cam.shape[0] == 0:
         return (cam.sum() * 0).expand(0, 1, height * width)
-    return _RenderFromCamera.apply(cam, volume, spec, int(height), int(width))
+    return _RenderFromCamera.apply(cam, volume, spec, int(height), int(width), volume_storage)
 
 
-def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w: int = 0, n_channels=None, work=None, pose_tail=None):
+def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w: int = 0, n_channels=None, work=None, pose_tail=None,
+           volume_storage: str = "float32"):
     """Functional form.  ``work``: optional cuda uint64/int64 scalar the kernel adds its count of
     volume-touching samples (trilinear) or voxel segments (siddon) to.  ``pose_tail``: a PoseTail -- source / target / img were
-    generated on the device from its pose parameters and carry no autograd history; the pose gradient goes to the parameters."""
+    generated on the device from its pose parameters and carry no autograd history; the pose gradient goes to the parameters.
+    ``volume_storage="float16"`` (trilinear, one channel, pose gradient only): march the half-tile copy of the volume -- bit for bit
+    the tiled float32 render of ``volume.clamp(-65504, 65504).half().float()``, at every launch size."""
     hu_map = None
+    check_volume_storage(volume_storage, spec.renderer)
+    if volume_storage == "float16":
+        _refuse_for_half(volume, mask, volume if type(volume).__name__ == "HUDensity" else None)
     if type(volume).__name__ == "HUDensity":   # (xvr_amd.data.HUDensity: a density that has not been written yet)
         volume.check_fresh()
         hu_map, volume = volume, volume.hu
@@ -626,11 +681,12 @@ def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w:
         if not (mask is not None and _packed_tiles_ok(spec, volume, mask, B, n, C) and YPAIR_TILES and YPAIR_TILES_PACKED):
             hu_map, volume = None, hu_map.materialize()
     if pose_tail is None:
-        return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, None, None, None)
+        return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, None, None, None, volume_storage)
     if mask is not None or spec.clip_to_volume == "batch" or source.requires_grad or target.requires_grad or img.requires_grad \
             or pose_tail.H * pose_tail.W != n or pose_tail.cam.shape[0] != B:
         raise ValueError("pose_tail: one channel, no batch alpha window, rays of the tail's own [B, H * W] detector without autograd history")
-    return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, pose_tail, pose_tail.rot, pose_tail.xyz)
+    return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, pose_tail, pose_tail.rot, pose_tail.xyz,
+                         volume_storage)
 
 
 def _packed_tiles_ok(spec, volume, mask, B, n, C) -> bool:
@@ -643,8 +699,11 @@ class _RendererBase(torch.nn.Module):
     renderer_name = ""
 
     def __init__(self, voxel_shift: float = 0.5, eps: float = 1e-8,
-                 filter_intersections_outside_volume: bool = True, **spec_overrides):
+                 filter_intersections_outside_volume: bool = True, volume_storage: str = "float32", **spec_overrides):
         super().__init__()
+        # how the forward stores the volume it marches ("float32": today's copies; "float16": half tiles, Trilinear only).  A
+        # property of the module, handed to render / render_from_camera -- not of RenderSpec, which describes the arithmetic
+        self.volume_storage = check_volume_storage(volume_storage, self.renderer_name)
         self.voxel_shift = voxel_shift
         self.eps = eps
         self.filter_intersections_outside_volume = filter_intersections_outside_volume
@@ -682,10 +741,10 @@ class Trilinear(_RendererBase):
 
     def __init__(self, near: float = 0.0, far: float = 1.0, mode: str = "bilinear",
                  filter_intersections_outside_volume: bool = True, voxel_shift: float = 0.5,
-                 eps: float = 1e-8, **spec_overrides):
+                 eps: float = 1e-8, volume_storage: str = "float32", **spec_overrides):
         if mode != "bilinear":
             raise NotImplementedError("Trilinear supports mode='bilinear' only")
-        super().__init__(voxel_shift, eps, filter_intersections_outside_volume, **spec_overrides)
+        super().__init__(voxel_shift, eps, filter_intersections_outside_volume, volume_storage, **spec_overrides)
         self.near, self.far, self.mode = near, far, mode
 
     def make_spec(self, n_points: int = 500, align_corners: bool = False) -> RenderSpec:
@@ -693,7 +752,8 @@ class Trilinear(_RendererBase):
 
     def forward(self, volume, source, target, img, n_points: int = 500, align_corners: bool = False, mask=None, pose_tail=None):
         spec = self.make_spec(n_points, align_corners)
-        return render(volume, source, target, img, spec, mask, self._grid_w(target.shape[1]), self._n_channels(mask), pose_tail=pose_tail)
+        return render(volume, source, target, img, spec, mask, self._grid_w(target.shape[1]), self._n_channels(mask), pose_tail=pose_tail,
+                      volume_storage=self.volume_storage)
 
 
 class Siddon(_RendererBase):
@@ -703,10 +763,10 @@ class Siddon(_RendererBase):
 
     def __init__(self, mode: str = "nearest", stop_gradients_through_grid_sample: bool = False,
                  filter_intersections_outside_volume: bool = True, voxel_shift: float = 0.5,
-                 eps: float = 1e-8, **spec_overrides):
+                 eps: float = 1e-8, volume_storage: str = "float32", **spec_overrides):
         if mode != "nearest":
             raise NotImplementedError("Siddon supports mode='nearest' only")
-        super().__init__(voxel_shift, eps, filter_intersections_outside_volume, **spec_overrides)
+        super().__init__(voxel_shift, eps, filter_intersections_outside_volume, volume_storage, **spec_overrides)
         self.mode = mode
         self.stop_gradients_through_grid_sample = stop_gradients_through_grid_sample
 
