@@ -381,6 +381,42 @@ int xvr_drr_hu_stats(const float* hu, long long n, void* stats, void* stream);
 int xvr_drr_hu_to_density(const float* hu, long long n, const void* stats, float bone_multiplier,
                           float* density, void* stream);
 
+/*
+ * Volume reconstruction: what consumes the voxel gradient of the backward calls.  Both are streaming passes
+ * over the volume, enqueued on `stream`, without host synchronisation.
+ *
+ * xvr_drr_tv_smooth: the smoothed isotropic total variation of volume [D0][D1][D2], forward differences with Neumann faces,
+ *     d_a(i) = w_a (V[i + e_a] - V[i])   (0 where i + e_a is outside),   n(i) = sqrt(d_0^2 + d_1^2 + d_2^2 + eps^2),
+ *     TV = sum_i (n(i) - eps),   dTV/dV[i] = -(w_0 d_0(i) + w_1 d_1(i) + w_2 d_2(i)) / n(i) + sum_a w_a d_a(i - e_a) / n(i - e_a)
+ * (terms with i - e_a outside dropped).  lambda * dTV/dV is ADDED into grad_accum [D0][D1][D2] (NULL: value only) -- a gather, no
+ * atomics -- and lambda * TV is WRITTEN to value[0] (NULL: gradient only; not both NULL).  True square roots and divisions: a
+ * constant volume gives exactly 0 for both.  The value is a fixed-order sum in doubles: identical bits on every run.  A non-finite
+ * voxel propagates to its neighbours' gradients and to the value.  `workspace`: xvr_drr_tv_smooth_workspace_bytes() bytes, 8-byte
+ * aligned, needed (and overwritten) only when `value` is given; no initial state.  Every axis must be at least 2, eps > 0.
+ * The factors are doubles: the gradient uses them rounded to float, the value's terms are evaluated in doubles from the float
+ * voxels, so that lambda * TV is right to the rounding of its one float result.
+ * 16-byte accesses where D2 % 4 == 0 and volume / grad_accum are 16-byte aligned, scalar ones otherwise.
+ */
+size_t xvr_drr_tv_smooth_workspace_bytes(int D0, int D1, int D2);
+int xvr_drr_tv_smooth(const float* volume, int D0, int D1, int D2, double w0, double w1, double w2, double eps, double lambda,
+                      float* grad_accum, float* value, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * xvr_drr_volume_adam_step: one projected Adam step over n voxels, in place, one pass (reads volume, grad, exp_avg, exp_avg_sq;
+ * writes volume, exp_avg, exp_avg_sq).  Per voxel, with g = grad (-grad with `maximize`):
+ *     g not finite:  volume, exp_avg, exp_avg_sq stay as they are and *skipped (a device counter the caller owns and zeroes;
+ *                    NULL: not counted) goes up by one -- the brick-local splats poison a voxel with NaN when a fixed-point sum
+ *                    leaves its range, and that must not reach the moments;
+ *     otherwise:     m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *                    p = p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps);  p = min(max(p, lo), hi)
+ * bc1 = 1 - beta1^t, bc2 = 1 - beta2^t for step t = 1, 2, ... are the caller's (hyper-parameters are doubles: 1 - beta2 taken from
+ * a float beta2 would be off by 1e-5 of itself).  lo / hi may be -INFINITY / +INFINITY; lo > hi, eps <= 0, bc <= 0 are refused.
+ * float4 accesses where the four buffers are 16-byte aligned (any n: the n % 4 tail is scalar), scalar ones otherwise.
+ */
+int xvr_drr_volume_adam_step(float* volume, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr,
+                             double beta1, double beta2, double eps, double bc1, double bc2, float lo, float hi, int maximize,
+                             unsigned* skipped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

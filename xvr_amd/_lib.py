@@ -143,6 +143,11 @@ EXPORTS = {
     "xvr_drr_jac_to_camera_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
     "xvr_drr_jac_to_camera_backward": ([_P, _P, _P, _I, _I, _I, _P, _P, ctypes.c_size_t, _P], ctypes.c_int),
     "xvr_drr_jac_to_pose_backward": ([_P, _P, _P, _I, _I, _I, _P, _P, _I, _AX, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], ctypes.c_int),
+    "xvr_drr_tv_smooth_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
+    "xvr_drr_tv_smooth": ([_P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P,
+                           ctypes.c_size_t, _P], ctypes.c_int),
+    "xvr_drr_volume_adam_step": ([_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_double, ctypes.c_float, ctypes.c_float, _I, _P, _P], ctypes.c_int),
     "xvr_pose_camera_forward": ([_P, _P, _I, _AX, _P, _P, _P, _P], ctypes.c_int),
     "xvr_pose_camera_backward": ([_P, _P, _I, _AX, _P, _P, _P, _P, _P], ctypes.c_int),
     "xvr_pose_geodesic": ([_P, _P, _I, ctypes.c_float, ctypes.c_float, _P, _P, _P], ctypes.c_int),

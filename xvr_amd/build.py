@@ -14,7 +14,8 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 SRC = [PKG / "csrc" / f for f in ("drr_trilinear.hip", "drr_siddon.hip", "drr_gather.hip", "drr_rays.hip", "drr_api.hip",
-                                  "sim_kernels.hip", "volume_kernels.hip", "pose_kernels.hip", "aug_kernels.hip")]
+                                  "sim_kernels.hip", "volume_kernels.hip", "pose_kernels.hip", "aug_kernels.hip",
+                                  "recon_kernels.hip")]
 HDR = [ROOT / "include" / "xvr_drr.h", ROOT / "include" / "xvr_sim.h", ROOT / "include" / "xvr_pose.h",
        PKG / "csrc" / "drr_common.hiph", PKG / "csrc" / "drr_splat.hiph", PKG / "csrc" / "drr_siddon_splat.hiph",
        PKG / "csrc" / "j2c_device.hiph", PKG / "csrc" / "pose_device.hiph",
