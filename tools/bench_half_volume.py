@@ -78,7 +78,7 @@ def main():
     drrs = {s: DRR(subject, 1020.0, H, delx, renderer="trilinear", reverse_x_axis=False, volume_storage=s).to(dev) for s in ("float32", "float16")}
     rot0, xyz0 = deepfluoro_poses(B, seed=0).convert("euler_angles", "ZXY")
     rot, xyz = rot0.to(dev).requires_grad_(True), xyz0.to(dev).requires_grad_(True)
-    if not renderers._use_ypairs(drrs["float32"].renderer.make_spec(args.n_points), drrs["float32"].density, B, H * H):
+    if renderers.plan_volume(drrs["float32"].renderer.make_spec(args.n_points), tuple(vol.shape), B, H * H).kind != "ypairs":
         raise SystemExit("bench_half_volume: at this size the fp32 module does not take the tiled copy; nothing to compare")
 
     # pack passes, alternating, each between its own pair of events

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .renderers import _ptr, _stream, _timed, make_cspec
+from .renderers import _ptr, _stream, _timed, _volume_for_launch, make_cspec, plan_volume
 
 __all__ = ["PoseCamera", "pose_camera", "RegistrationStage", "axes_of"]
 
@@ -141,25 +141,18 @@ class RegistrationStage:
         self.graph, self.graph_len = None, 1
 
     def _bind_volume(self):
-        """The render-ready copy of the (static) volume a launch of this size marches, as the autograd path chooses it
-        (renderers._RenderFromCamera): the tiled y-pair copy for trilinear launches of >= 2048 wavefronts, the bricked copy for Siddon
-        where it serves; built once per volume version, at first sight -- a registration renders the same volume hundreds of times.
+        """The render-ready copy of the volume a launch of this size marches, as ``renderers.plan_volume`` decides for a ``static``
+        volume: the tiled y-pair copy for trilinear launches of >= 2048 wavefronts, the bricked copy for Siddon where it serves, half
+        tiles at any size; built once per volume version, at first sight -- a registration renders the same volume hundreds of times.
         (One 512^2 pose is in the latency regime, where the layout does not matter: 184-194 us on either, alternating runs,
         profiles/r06_small_batch_tiles.txt; eight starts as one batch gain 2 %: 0.241 -> 0.236 ms per pose-iteration.)"""
-        from . import renderers as R
         vol = self.drr.density
         if self._vol_version == (vol.data_ptr(), vol._version):
             return
-        pairs, layout = None, 0
-        if getattr(self.drr.renderer, "volume_storage", "float32") == "float16":   # the module's half tiles, whatever the launch size
-            R._refuse_for_half(vol, None, None)
-            pairs, layout = R._half_volume(self.lib, vol), 4
-        elif R._use_ypairs(self.rspec, vol, self.B, self.n):
-            pairs, layout = R._layout_copy(self.lib, vol, "ypairs", first_sight=True), (3 if R.YPAIR_TILES else 1)
-        elif R._use_bricks(self.rspec, vol, self.B, self.n):
-            pairs, layout = R._brick_volume(self.lib, vol), 2
-        self.vol_render = pairs if pairs is not None else vol
-        self.cspec = make_cspec(tuple(vol.shape), self.rspec, self.W, volume_layout=layout if pairs is not None else 0)
+        plan = plan_volume(self.rspec, tuple(vol.shape), self.B, self.n, storage=getattr(self.drr.renderer, "volume_storage", "float32"),
+                           static=True)
+        self.vol_render, _, layout = _volume_for_launch(self.lib, plan, vol)
+        self.cspec = make_cspec(tuple(vol.shape), self.rspec, self.W, volume_layout=layout)
         if self._vol_version is not None:
             self.graph = None        # (the captured launches hold the old copy's pointer)
         self._vol_version = (vol.data_ptr(), vol._version)

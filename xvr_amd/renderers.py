@@ -19,6 +19,9 @@ raises (python exceptions only -- the reference's trainer catches them per step,
 from __future__ import annotations
 
 import ctypes
+import os as _os
+import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -89,7 +92,7 @@ _WORKSPACES = {}
 # a sum found in the guard band at a flush means the bound on a voxel's sum was optimistic: the voxels are poisoned with NaN (loud
 # downstream, no host sync) and word 2 of the workspace is set.  XVR_DRR_CHECK_OVERFLOW=1 reads that word after every backward (one
 # device -> host sync per step) and raises; last_backward_overflowed() reads it on demand.
-CHECK_OVERFLOW = __import__("os").environ.get("XVR_DRR_CHECK_OVERFLOW", "0") == "1"
+CHECK_OVERFLOW = _os.environ.get("XVR_DRR_CHECK_OVERFLOW", "0") == "1"
 # (count, hook) | None.  With count > 1 the voxel gradient of a backward is computed in `count` x slabs (whole planes of 16^3 bricks),
 # one launch per slab, and hook(i, grad_volume[x0:x1]) is called on the current stream's timeline right after slab i's launch: an
 # async collective issued there (torch.distributed orders it behind the stream's work so far) overlaps the remaining slabs
@@ -129,13 +132,20 @@ def _workspace(lib, B, n, shape, device, cspec=None, cells=False):
     return ws, ws.numel() * 4
 
 
+def _j2c_workspace(lib, B, H, W, device):
+    """Scratch of the jacobian -> camera / -> pose kernels per (device, stream): zero-filled once; every call leaves it ready again."""
+    nbytes = lib.xvr_drr_jac_to_camera_workspace_bytes(B, H, W)
+    key = ("j2c", device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _WORKSPACES.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _WORKSPACES[key] = torch.zeros((nbytes + 3) // 4, device=device, dtype=torch.float32)
+    return ws
+
+
 # Mask -> channels renders with at most 16 labels use a copy of the volume that carries every voxel's label
 # in its low 4 mantissa bits (xvr_drr_pack_labels; include/xvr_drr.h): the label lookup then costs no gather.
 # The density seen by the render moves by <= 15 ulp (1.8e-6 relative).  False (or XVR_DRR_PACK_LABELS=0)
 # keeps the separate lookup in the mask volume.
-import os as _os
-import weakref
-
 PACK_LABELS = _os.environ.get("XVR_DRR_PACK_LABELS", "1") != "0"
 
 
@@ -188,19 +198,18 @@ def _packed_volume(lib, volume, mask):
     return packed
 
 
-def _packed_ypair_volume(lib, volume, mask, hu_map=None):
-    """The y-pair interleaved copy of the label-carrying volume, written in ONE pass over (volume, mask)
-    (xvr_drr_pack_labels_ypairs): masked renders of large launches take it at once -- their volume is typically the fresh
-    HU -> density map of a training step, rendered exactly twice (trainer.py:185-230), for which the "third render" rule of
+def _packed_ypair_volume(lib, volume, mask, tiles, hu_map=None):
+    """The y-pair interleaved copy (``tiles``: 2 x 8 tiles, else rows) of the label-carrying volume, written in ONE pass over
+    (volume, mask) (xvr_drr_pack_labels_ypairs): masked renders of large launches take it at once -- their volume is typically the
+    fresh HU -> density map of a training step, rendered exactly twice (trainer.py:185-230), for which the "third render" rule of
     _layout_copy never fires.  0.75 ms at 512^3 against 0.36 for the labels alone; each of the two renders then saves ~1 ms."""
     D0, D1, D2 = volume.shape
     key = (mask.data_ptr(), mask._version, volume._version)
     slot = _cache_slot(volume)
-    tiles = YPAIR_TILES and YPAIR_TILES_PACKED
     key = key + (tiles, None if hu_map is None else hu_map.multiplier)
     hit = slot.get("packed_ypairs")
     if hit is not None and hit[0] == key and hit[2]() is mask:
-        return hit[1], (3 if tiles else 1)
+        return hit[1]
     nbytes, pack = ((lib.xvr_drr_ytiles_bytes, lib.xvr_drr_pack_labels_ytiles) if tiles
                     else (lib.xvr_drr_ypairs_bytes, lib.xvr_drr_pack_labels_ypairs))
     buf = hit[1] if hit is not None and hit[1].numel() * 4 == nbytes(D0, D1, D2) and hu_map is not None else \
@@ -213,13 +222,13 @@ def _packed_ypair_volume(lib, volume, mask, hu_map=None):
         rc = _timed("pack_labels_ypairs", pack, _ptr(volume), _ptr(mask), D0, D1, D2, _ptr(buf), _stream())
     _lib.check(rc, "xvr_drr_pack_labels_ypairs")
     slot["packed_ypairs"] = (key, buf, weakref.ref(mask))
-    return buf, (3 if tiles else 1)
+    return buf
 
 
 # One-channel trilinear renders of LARGE launches march a y-pair interleaved copy of the volume (xvr_drr_pack_ypairs): two
 # 16-byte gathers per sample instead of four 8-byte ones -- the march is bound by the texture-address rate per gather
 # instruction -- with identical output bits.  Costs twice the volume's memory (cached ON the volume tensor object, keyed by
-# its version counter, built the third time a version is rendered: see _ypair_volume).  False (or XVR_DRR_YPAIRS=0):
+# its version counter, built the third time a version is rendered: see _layout_copy).  False (or XVR_DRR_YPAIRS=0):
 # natural layout.
 YPAIR_LAYOUT = _os.environ.get("XVR_DRR_YPAIRS", "1") != "0"
 # ... and that copy is cut into 2 x 8 tiles overlapping along z (xvr_drr_pack_ytiles, volume_layout 3; round 4): the forward is
@@ -245,11 +254,11 @@ YPAIR_FIRST_SIGHT_SAMPLES_PER_VOXEL = float(_os.environ.get("XVR_DRR_YPAIRS_FIRS
 
 
 def _layout_copy(lib, volume, kind, first_sight=False):
-    """The y-pair (``kind`` = "ypairs") or bricked ("bricks") copy of ``volume``, or None the first LAYOUT_COPY_AFTER[kind]
-    times a version of it is seen.  The y-pair copy costs 0.54 ms at 512^3 and saves ~0.7 ms per render: it waits for the third
-    render, i.e. for a volume that is rendered again and again unchanged (registration, the benchmark, a fixed CT) -- a volume
-    that changes between renders (voxels being optimised) stays on the natural layout; the fresh HU -> density map of every
-    training step, rendered exactly twice with a mask (trainer.py:185-230), gets labels and y-pairs in one pass at first
+    """The y-pair (``kind`` = "ypairs"), bricked ("bricks") or half-tile ("htiles") copy of ``volume``, or None the first
+    LAYOUT_COPY_AFTER[kind] times a version of it is seen.  The y-pair copy costs 0.54 ms at 512^3 and saves ~0.7 ms per render: it
+    waits for the third render, i.e. for a volume that is rendered again and again unchanged (registration, the benchmark, a fixed
+    CT) -- a volume that changes between renders (voxels being optimised) stays on the natural layout; the fresh HU -> density map
+    of every training step, rendered exactly twice with a mask (trainer.py:185-230), gets labels and y-pairs in one pass at first
     sight (_packed_ypair_volume).  The bricked copy for Siddon saves 1.3 ms per render and is built at first sight."""
     D0, D1, D2 = volume.shape
     key = (volume._version, YPAIR_TILES)
@@ -279,13 +288,6 @@ def _layout_copy(lib, volume, kind, first_sight=False):
     return buf
 
 
-def _ypair_volume(lib, volume, samples=0):
-    """-> (copy or None, its volume_layout code: 3 = 2 x 8 tiles, 1 = rows).  ``samples``: nominal samples of the launch asking
-    (B n n_points): a launch large enough to pay for the tiled copy gets it at first sight (YPAIR_FIRST_SIGHT_SAMPLES_PER_VOXEL)."""
-    first = YPAIR_TILES and samples > YPAIR_FIRST_SIGHT_SAMPLES_PER_VOXEL * volume.numel()
-    return _layout_copy(lib, volume, "ypairs", first), (3 if YPAIR_TILES else 1)
-
-
 # ``volume_storage="float16"`` (Trilinear): every forward marches the tiled y-pair copy in IEEE halves (xvr_drr_pack_htiles,
 # volume_layout 4) -- the render of the volume rounded to half, an opt-in accuracy trade (DESIGN.md section 4.6).  The copy is a
 # third kind in the cache above, built at first sight (the user asked for it) and rebuilt when the tensor's version changes.
@@ -301,15 +303,6 @@ def check_volume_storage(volume_storage, renderer="trilinear"):
     return volume_storage
 
 
-def _half_volume(lib, volume):
-    """The half-tile copy of ``volume`` (a contiguous float32 [D0, D1, D2] tensor): the ONLY thing a float16-storage render reads."""
-    D0, D1, D2 = volume.shape
-    if min(D0, D1, D2) < 2 or D2 > HTILES_MAX_D2 or ((D0 + 1) // 2) * (D1 + 1) * ((D2 - 2) // 15 + 1) * 32 >= 2 ** 31:
-        raise ValueError(f"volume_storage='float16': a volume of shape {(D0, D1, D2)} is outside the half tiles' range "
-                         f"(every axis >= 2, the last at most {HTILES_MAX_D2}, fewer than 2^31 tile entries)")
-    return _layout_copy(lib, volume, "htiles", first_sight=True)
-
-
 def _refuse_for_half(volume, mask, hu_map):
     """What float16 storage does not render raises -- never a picture from the float32 volume instead."""
     if hu_map is not None:
@@ -321,11 +314,6 @@ def _refuse_for_half(volume, mask, hu_map):
     if volume.requires_grad:
         raise NotImplementedError("volume_storage='float16': no voxel gradient through the rounded copy; detach the density, or use "
                                   "float32 storage")
-
-
-def _brick_volume(lib, volume):
-    """(2 x 2 x 8-voxel bricks for the Siddon forward, xvr_drr_pack_bricks; cached by the y-pair copy's rule)"""
-    return _layout_copy(lib, volume, "bricks")
 
 
 # ... also for the non-exact index maps that the slab march serves since round 5 (norm_dims_offset = +1, align_corners: maps under
@@ -343,31 +331,80 @@ def _siddon_map_in_bounds(spec, shape) -> bool:
     return True
 
 
-def _use_bricks(spec, volume, B, n, C=1):
-    """(large one-channel Siddon launches: 10.3 -> 9.7 ms at C3 on the merge walk, 6.9 -> 4.9 on the slab march.  Labels packed into
-    the taps measured SLOWER with bricks -- their walk is bound by arithmetic the brick address adds to.)"""
-    D0, D1, D2 = volume.shape
+class VolumePlan(NamedTuple):
+    """Which render-ready copy of the volume a forward launch marches: what plan_volume decides and _volume_for_launch carries out."""
+    kind: str | None = None         # the copy's slot in the cache: "ypairs", "htiles", "bricks", "packed", "packed_ypairs"; None: no copy
+    layout: int = 0                 # the CSpec's volume_layout once the copy is served (0: the natural layout)
+    first_sight: bool = False       # built at the first render of a volume version, not after LAYOUT_COPY_AFTER[kind] renders of it
+    labels_in_taps: bool = False    # the labels ride in the copy's mantissa bits: the kernel gets no mask pointer
+    hu_in_pack: bool = False        # a lazy HU density is mapped inside the packing pass and never written
+
+
+def plan_volume(spec: RenderSpec, shape, B, n, C=1, storage="float32", masked=False, aligned=True, contiguous=True, lazy_hu=False,
+                static=False) -> VolumePlan:
+    """The one decision on a forward launch's volume copy, from values alone (the knobs above at call time, and the library's
+    ``siddon_slab`` / ``fwd_split`` options for Siddon's non-exact maps): nothing is allocated, launched or cached.  ``aligned``:
+    volume and mask, as the kernel will be handed them, start on 16 bytes; ``contiguous``: they were as the caller gave them (the
+    lazy HU route packs the caller's own buffers).  ``static``: the caller renders this volume again and again.
+    The kinds exclude one another -- half tiles and y-pairs are trilinear, bricks Siddon with one channel, label packing takes 2 to
+    16 channels -- so the order below (half, labels, y-pairs, bricks) is a reading order, not a priority.  Where the callers differ:
+    the autograd renders give a y-pair copy LAYOUT_COPY_AFTER renders of a version to pay for itself unless the launch alone does
+    (YPAIR_FIRST_SIGHT_SAMPLES_PER_VOXEL); a registration stage (``static``) renders one volume hundreds of times and builds it at
+    first sight whatever the launch size (the bricked copy follows its count, 0, at every caller).  Half storage is the whole-ray
+    tiled copy at every launch size, so nothing after it is asked -- vacuous for bricks, which float16
+    storage (trilinear only) never meets."""
+    D0, D1, D2 = shape
     waves = B * ((n + 63) // 64)
-    exact = spec.norm_dims_offset == 0 and not spec.align_corners
-    if not exact:
-        # (the bricked copy serves these maps through the slab march ONLY -- xvr_drr_siddon_forward refuses it otherwise: the
-        #  march's own conditions, mirrored; everything else keeps the natural layout and the merge walk)
-        if not (BRICK_NX and _lib.get_option("siddon_slab") == 1 and _lib.get_option("fwd_split") in (0, 1)
-                and _siddon_map_in_bounds(spec, (D0, D1, D2)) and D1 * D2 < 2 ** 24 and D0 * D1 * D2 < 2 ** 29
-                and (D0 + D1 + D2 + 6) * 4 <= 48 * 1024 and waves > YPAIR_MIN_WAVEFRONTS):
-            return False
-    return (BRICK_LAYOUT and spec.renderer == "siddon" and C == 1 and waves >= YPAIR_MIN_WAVEFRONTS
-            and ((D0 + 1) // 2) * ((D1 + 1) // 2) * ((D2 + 7) // 8) * 32 < 2 ** 31 and min(D0, D1, D2) >= 2)
-
-
-def _use_ypairs(spec, volume, B, n):
-    """(one channel, or labels packed into the volume's mantissa bits -- never with a separate mask volume)"""
-    D0, D1, D2 = volume.shape
-    elements = ((D0 + 1) // 2) * (D1 + 1) * ((D2 - 2) // 7 + 1) * 32 if YPAIR_TILES else D0 * (D1 + 1) * D2 * 2
+    if storage == "float16":    # (masks, lazy HU densities and voxel gradients have been refused: _refuse_for_half)
+        return VolumePlan("htiles", 4, True)
+    # y-pairs: one channel, or labels packed into the volume's mantissa bits -- never with a separate mask volume.
     # (tiles: the kernel's z / 7 is a multiply-shift that holds below 8192 -- xvr_drr_trilinear_forward and xvr_drr_pack_ytiles
     #  refuse longer volumes, which therefore stay on the natural layout instead of raising at render time)
-    return (YPAIR_LAYOUT and spec.renderer == "trilinear" and B * ((n + 63) // 64) >= YPAIR_MIN_WAVEFRONTS
-            and elements < 2 ** 31 and min(D0, D1, D2) >= 2 and (D2 < 8192 or not YPAIR_TILES))
+    elements = ((D0 + 1) // 2) * (D1 + 1) * ((D2 - 2) // 7 + 1) * 32 if YPAIR_TILES else D0 * (D1 + 1) * D2 * 2
+    ypairs = (YPAIR_LAYOUT and spec.renderer == "trilinear" and waves >= YPAIR_MIN_WAVEFRONTS
+              and elements < 2 ** 31 and min(D0, D1, D2) >= 2 and (D2 < 8192 or not YPAIR_TILES))
+    if masked:
+        if not (PACK_LABELS and 2 <= C <= 16 and aligned):
+            return VolumePlan()    # the separate lookup in the mask volume, on the natural layout
+        if not ypairs:
+            return VolumePlan("packed", 0, True, True)
+        # labels AND y-pairs in one pass; the one consumer that takes a HU map inside its own pass is its tiled form
+        tiles = YPAIR_TILES and YPAIR_TILES_PACKED
+        return VolumePlan("packed_ypairs", 3 if tiles else 1, True, True, bool(lazy_hu and contiguous and tiles))
+    if ypairs:
+        pays_at_once = YPAIR_TILES and B * n * spec.n_points > YPAIR_FIRST_SIGHT_SAMPLES_PER_VOXEL * D0 * D1 * D2
+        return VolumePlan("ypairs", 3 if YPAIR_TILES else 1, bool(static or pays_at_once or LAYOUT_COPY_AFTER["ypairs"] < 1))
+    # bricks: large one-channel Siddon launches (10.3 -> 9.7 ms at C3 on the merge walk, 6.9 -> 4.9 on the slab march.  Labels packed
+    # into the taps measured SLOWER with bricks -- their walk is bound by arithmetic the brick address adds to.)
+    bricks = (BRICK_LAYOUT and spec.renderer == "siddon" and C == 1 and waves >= YPAIR_MIN_WAVEFRONTS
+              and ((D0 + 1) // 2) * ((D1 + 1) // 2) * ((D2 + 7) // 8) * 32 < 2 ** 31 and min(D0, D1, D2) >= 2)
+    if bricks and (spec.norm_dims_offset != 0 or spec.align_corners):
+        # (the bricked copy serves the non-exact maps through the slab march ONLY -- xvr_drr_siddon_forward refuses it otherwise: the
+        #  march's own conditions, mirrored; everything else keeps the natural layout and the merge walk)
+        bricks = (BRICK_NX and _lib.get_option("siddon_slab") == 1 and _lib.get_option("fwd_split") in (0, 1)
+                  and _siddon_map_in_bounds(spec, (D0, D1, D2)) and D1 * D2 < 2 ** 24 and D0 * D1 * D2 < 2 ** 29
+                  and (D0 + D1 + D2 + 6) * 4 <= 48 * 1024 and waves > YPAIR_MIN_WAVEFRONTS)
+    return VolumePlan("bricks", 2, LAYOUT_COPY_AFTER["bricks"] < 1) if bricks else VolumePlan()
+
+
+def _volume_for_launch(lib, plan: VolumePlan, volume, mask=None, hu_map=None):
+    """-> (the tensor whose pointer the forward kernel gets, the mask it gets or None, the CSpec's volume_layout) for contiguous
+    ``volume`` / ``mask``: the only caller of the pack entry points and of the cache.  A "ypairs" / "bricks" copy still inside its
+    LAYOUT_COPY_AFTER count is not built: the natural volume, layout 0.  ``hu_map``: only with ``plan.hu_in_pack``."""
+    if plan.kind is None:
+        return volume, mask, 0
+    if plan.kind == "packed":
+        return _packed_volume(lib, volume, mask), None, 0
+    if plan.kind == "packed_ypairs":
+        return _packed_ypair_volume(lib, volume, mask, plan.layout == 3, hu_map), None, plan.layout
+    if plan.kind == "htiles":   # the ONLY thing a float16-storage render reads
+        _refuse_for_half(volume, mask, hu_map)   # (render has, before its other checks; a registration stage arrives here first)
+        D0, D1, D2 = volume.shape
+        if min(D0, D1, D2) < 2 or D2 > HTILES_MAX_D2 or ((D0 + 1) // 2) * (D1 + 1) * ((D2 - 2) // 15 + 1) * 32 >= 2 ** 31:
+            raise ValueError(f"volume_storage='float16': a volume of shape {(D0, D1, D2)} is outside the half tiles' range "
+                             f"(every axis >= 2, the last at most {HTILES_MAX_D2}, fewer than 2^31 tile entries)")
+    copy = _layout_copy(lib, volume, plan.kind, plan.first_sight)
+    return (volume, mask, 0) if copy is None else (copy, mask, plan.layout)
 
 
 class PoseTail:
@@ -396,11 +433,7 @@ class PoseTail:
         rot, xyz, cam, G, pose_jac = tensors
         rot_c, xyz_c, B = rot.detach().contiguous(), xyz.detach().contiguous(), cam.shape[0]
         g_rot, g_xyz = torch.empty_like(rot_c), torch.empty_like(xyz_c)
-        nbytes = lib.xvr_drr_jac_to_camera_workspace_bytes(B, H, W)
-        key = ("j2c", cam.device, torch.cuda.current_stream(cam.device).cuda_stream)
-        ws = _WORKSPACES.get(key)
-        if ws is None or ws.numel() * 4 < nbytes:   # zero-filled once; every call leaves it ready for the next
-            ws = _WORKSPACES[key] = torch.zeros((nbytes + 3) // 4, device=cam.device, dtype=torch.float32)
+        ws = _j2c_workspace(lib, B, H, W, cam.device)
         rc = _timed("jac_to_pose_backward", lib.xvr_drr_jac_to_pose_backward, _ptr(jac), _ptr(gout), _ptr(cam), B, H, W,
                     _ptr(rot_c), _ptr(xyz_c), kind, axes_of(convention if kind == 0 else "ZXY"), _ptr(G),
                     _ptr(pose_jac), _ptr(g_rot), _ptr(g_xyz), None, _ptr(ws), ws.numel() * 4, _stream())
@@ -415,39 +448,22 @@ class _Render(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, volume, source, target, img, mask, spec: RenderSpec, ray_grid_w: int, C: int, work, hu_map=None,
-                tail=None, rot=None, xyz=None, volume_storage="float32"):
+                tail=None, rot=None, xyz=None, plan=VolumePlan()):
         lib = _lib.load()
         D0, D1, D2 = volume.shape
         B, n, _ = target.shape
-        vol_c = volume.contiguous()
+        vol_c, msk_c = volume, mask     # (contiguous: render() planned for the very tensors the kernel is handed)
         src_c = source.reshape(B, 3).contiguous()
         tgt_c = target.contiguous()
         len_c = img.reshape(B, n).contiguous()
-        msk_c = mask.contiguous() if mask is not None else None
         need_pose = any(ctx.needs_input_grad[1:4]) or (tail is not None and any(ctx.needs_input_grad[11:13]))
         use_jac = need_pose  # with a mask: the jacobian of the channel sum (see backward)
         ctx.tail = tail.meta() if tail is not None else None
         out = torch.empty(B, C, n, device=volume.device, dtype=torch.float32)
         jac = torch.empty(B, n, _lib.JAC_STRIDE, device=volume.device, dtype=torch.float32) if use_jac else None
         fn = lib.xvr_drr_trilinear_forward if spec.renderer == "trilinear" else lib.xvr_drr_siddon_forward
-        vol_f, msk_f = vol_c, msk_c
-        pairs, pairs_layout = None, 1
-        half = volume_storage == "float16"
-        if half:    # (render() has refused masks, lazy HU densities and voxel gradients)
-            pairs, pairs_layout = _half_volume(lib, vol_c), 4
-        elif msk_c is not None and PACK_LABELS and 2 <= C <= 16 and vol_c.data_ptr() % 16 == 0 and msk_c.data_ptr() % 16 == 0:
-            if _use_ypairs(spec, vol_c, B, n):
-                (pairs, pairs_layout), msk_f = _packed_ypair_volume(lib, vol_c, msk_c, hu_map), None   # labels in the taps AND the y-pair layout, one pass
-            else:
-                vol_f, msk_f = _packed_volume(lib, vol_c, msk_c), None     # labels ride in the taps
-        if pairs is None and msk_f is None and _use_ypairs(spec, vol_c, B, n):
-            pairs, pairs_layout = _ypair_volume(lib, vol_f, B * n * spec.n_points)
-        bricks = _brick_volume(lib, vol_f) if msk_f is None and not half and _use_bricks(spec, vol_c, B, n, C) else None
-        if pairs is not None:
-            vol_f = pairs                                              # (of the label-carrying copy when there is one)
-        if bricks is not None:
-            vol_f = bricks
-        cs = make_cspec((D0, D1, D2), spec, ray_grid_w, volume_layout=pairs_layout if pairs is not None else (2 if bricks is not None else 0))
+        vol_f, msk_f, layout = _volume_for_launch(lib, plan, vol_c, msk_c, hu_map)
+        cs = make_cspec((D0, D1, D2), spec, ray_grid_w, volume_layout=layout)
         window = None
         if spec.renderer == "trilinear" and spec.clip_to_volume == "batch":
             # ONE alpha window for the whole call, reduced on the device from its rays (no host round trip): the kernels read
@@ -463,8 +479,6 @@ class _Render(torch.autograd.Function):
                     _ptr(vol_f), _ptr(msk_f), D0, D1, D2, C, _ptr(src_c), _ptr(tgt_c), _ptr(len_c), B, n,
                     ctypes.byref(cs), _ptr(out), _ptr(jac), _ptr(work), _stream())
         _lib.check(rc, f"xvr_drr_{spec.renderer}_forward")
-        if hu_map is not None and pairs is None:
-            raise RuntimeError("internal: a lazy HU density reached a render that does not pack its own copy")
         ctx.spec, ctx.ray_grid_w, ctx.C = spec, ray_grid_w, C
         ctx.src_shape, ctx.img_shape = source.shape, img.shape
         ctx.window, ctx.hu_map = window, hu_map
@@ -578,26 +592,17 @@ class _RenderFromCamera(torch.autograd.Function):
     one channel: what the reference's registration loop differentiates."""
 
     @staticmethod
-    def forward(ctx, cam, volume, spec: RenderSpec, H: int, W: int, volume_storage="float32"):
+    def forward(ctx, cam, volume, spec: RenderSpec, H: int, W: int, plan=VolumePlan()):
         lib = _lib.load()
-        cam_c, vol_c = cam.contiguous(), volume.contiguous()
+        cam_c = cam.contiguous()
         B, n = cam_c.shape[0], H * W
-        half = volume_storage == "float16"
-        if half:
-            pairs, layout = _half_volume(lib, vol_c), 4
-        else:
-            pairs, layout = _ypair_volume(lib, vol_c, B * n * spec.n_points) if _use_ypairs(spec, vol_c, B, n) else (None, 0)
-        if pairs is None and _use_bricks(spec, vol_c, B, n):
-            pairs, layout = _brick_volume(lib, vol_c), 2               # (siddon: the bricked copy takes the same seat)
-        if pairs is None:
-            layout = 0
-        cs = make_cspec(tuple(vol_c.shape), spec, W, volume_layout=layout)
+        vol_f, _, layout = _volume_for_launch(lib, plan, volume)   # (siddon: the bricked copy takes the y-pair copy's seat)
+        cs = make_cspec(tuple(volume.shape), spec, W, volume_layout=layout)
         need = ctx.needs_input_grad[0]
         out = torch.empty(B, 1, n, device=cam.device, dtype=torch.float32)
         jac = torch.empty(B, n, _lib.JAC_STRIDE, device=cam.device, dtype=torch.float32) if need else None
         fn = lib.xvr_drr_trilinear_forward_camera if spec.renderer == "trilinear" else lib.xvr_drr_siddon_forward_camera
-        rc = _timed(f"{spec.renderer}_forward" + ("+jac" if need else ""), fn, _ptr(pairs if pairs is not None else vol_c), None,
-                    *vol_c.shape, 1, _ptr(cam_c),
+        rc = _timed(f"{spec.renderer}_forward" + ("+jac" if need else ""), fn, _ptr(vol_f), None, *volume.shape, 1, _ptr(cam_c),
                     B, H, W, ctypes.byref(cs), _ptr(out), _ptr(jac), None, _stream())
         _lib.check(rc, f"xvr_drr_{spec.renderer}_forward_camera")
         ctx.save_for_backward(cam_c, jac)
@@ -611,15 +616,15 @@ class _RenderFromCamera(torch.autograd.Function):
         H, W = ctx.hw
         B = cam_c.shape[0]
         g_cam = torch.empty_like(cam_c)
-        nbytes = lib.xvr_drr_jac_to_camera_workspace_bytes(B, H, W)
-        key = ("j2c", cam_c.device, torch.cuda.current_stream(cam_c.device).cuda_stream)
-        ws = _WORKSPACES.get(key)
-        if ws is None or ws.numel() * 4 < nbytes:   # zero-filled once; every call leaves it ready for the next
-            ws = _WORKSPACES[key] = torch.zeros((nbytes + 3) // 4, device=cam_c.device, dtype=torch.float32)
+        ws = _j2c_workspace(lib, B, H, W, cam_c.device)
         rc = _timed("jac_to_camera_backward", lib.xvr_drr_jac_to_camera_backward, _ptr(jac), _ptr(gout.contiguous()), _ptr(cam_c),
                     B, H, W, _ptr(g_cam), _ptr(ws), ws.numel() * 4, _stream())
         _lib.check(rc, "xvr_drr_jac_to_camera_backward")
         return g_cam, None, None, None, None, None
+
+
+def _is_lazy_hu(volume) -> bool:   # (xvr_amd.data.HUDensity: a density that has not been written yet)
+    return type(volume).__name__ == "HUDensity"
 
 
 def render_from_camera(volume, cam, spec: RenderSpec, height: int, width: int, volume_storage: str = "float32"):
@@ -627,14 +632,16 @@ def render_from_camera(volume, cam, spec: RenderSpec, height: int, width: int, v
     volume is treated as a constant (no voxel gradient on this path).  ``volume_storage``: as ``render``."""
     check_volume_storage(volume_storage, spec.renderer)
     if volume_storage == "float16":
-        _refuse_for_half(volume, None, volume if type(volume).__name__ == "HUDensity" else None)
+        _refuse_for_half(volume, None, volume if _is_lazy_hu(volume) else None)
     _check_gpu_f32("volume", volume)
     _check_gpu_f32("cam", cam)
     if volume.dim() != 3 or cam.dim() != 2 or cam.shape[1] != 24:
         raise ValueError("volume must be [D0, D1, D2] and cam [B, 24]")
     if cam.shape[0] == 0:
         return (cam.sum() * 0).expand(0, 1, height * width)
-    return _RenderFromCamera.apply(cam, volume, spec, int(height), int(width), volume_storage)
+    volume = volume.contiguous()
+    plan = plan_volume(spec, tuple(volume.shape), cam.shape[0], int(height) * int(width), storage=volume_storage)
+    return _RenderFromCamera.apply(cam, volume, spec, int(height), int(width), plan)
 
 
 def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w: int = 0, n_channels=None, work=None, pose_tail=None,
@@ -647,8 +654,8 @@ def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w:
     hu_map = None
     check_volume_storage(volume_storage, spec.renderer)
     if volume_storage == "float16":
-        _refuse_for_half(volume, mask, volume if type(volume).__name__ == "HUDensity" else None)
-    if type(volume).__name__ == "HUDensity":   # (xvr_amd.data.HUDensity: a density that has not been written yet)
+        _refuse_for_half(volume, mask, volume if _is_lazy_hu(volume) else None)
+    if _is_lazy_hu(volume):
         volume.check_fresh()
         hu_map, volume = volume, volume.hu
     for name, t in (("volume", volume), ("source", source), ("target", target), ("img", img)):
@@ -675,24 +682,28 @@ def render(volume, source, target, img, spec: RenderSpec, mask=None, ray_grid_w:
         # an empty batch (xvr's `img[keep]` can select nothing, trainer.py:202-204) renders to an empty
         # image that still hangs off the inputs' autograd graph
         return (source.sum() + target.sum() + img.sum() + 0 * volume.sum()).expand(B, C, n)
-    if hu_map is not None:
+    contiguous = volume.is_contiguous() and (mask is None or mask.is_contiguous())
+    mask = mask.contiguous() if mask is not None else None
+
+    def plan_for(volume, lazy_hu):
+        aligned = volume.data_ptr() % 16 == 0 and (mask is None or mask.data_ptr() % 16 == 0)
+        return plan_volume(spec, tuple(volume.shape), B, n, C, volume_storage, mask is not None, aligned, contiguous, lazy_hu)
+
+    if hu_map is None:
+        volume = volume.contiguous()
+    plan = plan_for(volume, hu_map is not None)
+    if hu_map is not None and not plan.hu_in_pack:
         # the one consumer that takes the HU map inside its own pass: a masked trilinear launch large enough for the tiled,
         # label-carrying y-pair copy, with nothing to differentiate w.r.t. the voxels; everything else gets the density written
-        if not (mask is not None and _packed_tiles_ok(spec, volume, mask, B, n, C) and YPAIR_TILES and YPAIR_TILES_PACKED):
-            hu_map, volume = None, hu_map.materialize()
+        hu_map, volume = None, hu_map.materialize().contiguous()
+        plan = plan_for(volume, False)
     if pose_tail is None:
-        return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, None, None, None, volume_storage)
+        return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, None, None, None, plan)
     if mask is not None or spec.clip_to_volume == "batch" or source.requires_grad or target.requires_grad or img.requires_grad \
             or pose_tail.H * pose_tail.W != n or pose_tail.cam.shape[0] != B:
         raise ValueError("pose_tail: one channel, no batch alpha window, rays of the tail's own [B, H * W] detector without autograd history")
     return _Render.apply(volume, source, target, img, mask, spec, int(ray_grid_w), C, work, hu_map, pose_tail, pose_tail.rot, pose_tail.xyz,
-                         volume_storage)
-
-
-def _packed_tiles_ok(spec, volume, mask, B, n, C) -> bool:
-    """Will _Render.forward render this masked launch from the label-carrying y-pair copy (_packed_ypair_volume)?"""
-    return (PACK_LABELS and 2 <= C <= 16 and volume.is_contiguous() and mask.is_contiguous() and volume.data_ptr() % 16 == 0
-            and mask.data_ptr() % 16 == 0 and _use_ypairs(spec, volume, B, n))
+                         plan)
 
 
 class _RendererBase(torch.nn.Module):
