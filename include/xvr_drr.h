@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define XVR_DRR_ABI_VERSION 12   /* (xvr_drr_jac_to_pose_backward, and volume_layout 4 with xvr_drr_htiles_bytes / xvr_drr_pack_htiles -- the tiled y-pair copy in IEEE halves -- were ADDED under 12: no existing entry point changed shape; tests/test_augment.py pins the number, and the binding refuses a library that lacks an export by name) 12: xvr_drr_trilinear_backward / xvr_drr_siddon_backward take slab_index, slab_count (an argument of the call where a process-wide option used to carry it); 11: xvr_sim_augment_* (the training step's X-ray augmentations); 10: xvr_sim_ncc_registration_step (the tail of a registration iteration in the similarity's launches); 9: xvr_drr_pack_hu_labels_ytiles, options siddon_splat / gather_splat = 3 / siddon_slab = 2, pose kind 6 (rotation_10d), non-exact Siddon index maps on the slab march and the brick splat, guard-banded fixed point; 8: volume_layout 3 + xvr_drr_pack_ytiles / _labels_ytiles (tiled y-pair copy), xvr_pose_camera_forward_param / xvr_pose_opt_step_param (device-resident registration for every parameterisation; xvr_pose_opt_state holds 13 parameters), xvr_sim_equalize_* write / take the normalised output, options tile_geom, siddon_slab, siddon_gather_fast; 7: xvr_drr_foreground, xvr_drr_pack_labels_ypairs, xvr_sim_dice_bool, xvr_sim_transform_* (xvr_sim.h), xvr_pose_convert_* (xvr_pose.h); 6: xvr_drr_spec.alpha_window + xvr_drr_alpha_window (clip_to_volume = 2); 5: xvr_drr_set_option / xvr_drr_get_option (the A/B switches are no longer getenv calls per launch); 4: volume_layout 2 + xvr_drr_pack_bricks (siddon forward); 3: xvr_drr_spec.volume_layout + xvr_drr_pack_ypairs; 2: xvr_sim_spec grew, camera-driven forwards, packed labels, xvr_pose.h */
+#define XVR_DRR_ABI_VERSION 12   /* (xvr_drr_voxel_gradient_plan, xvr_drr_jac_to_pose_backward, and volume_layout 4 with xvr_drr_htiles_bytes / xvr_drr_pack_htiles -- the tiled y-pair copy in IEEE halves -- were ADDED under 12: no existing entry point changed shape; tests/test_augment.py pins the number, and the binding refuses a library that lacks an export by name) 12: xvr_drr_trilinear_backward / xvr_drr_siddon_backward take slab_index, slab_count (an argument of the call where a process-wide option used to carry it); 11: xvr_sim_augment_* (the training step's X-ray augmentations); 10: xvr_sim_ncc_registration_step (the tail of a registration iteration in the similarity's launches); 9: xvr_drr_pack_hu_labels_ytiles, options siddon_splat / gather_splat = 3 / siddon_slab = 2, pose kind 6 (rotation_10d), non-exact Siddon index maps on the slab march and the brick splat, guard-banded fixed point; 8: volume_layout 3 + xvr_drr_pack_ytiles / _labels_ytiles (tiled y-pair copy), xvr_pose_camera_forward_param / xvr_pose_opt_step_param (device-resident registration for every parameterisation; xvr_pose_opt_state holds 13 parameters), xvr_sim_equalize_* write / take the normalised output, options tile_geom, siddon_slab, siddon_gather_fast; 7: xvr_drr_foreground, xvr_drr_pack_labels_ypairs, xvr_sim_dice_bool, xvr_sim_transform_* (xvr_sim.h), xvr_pose_convert_* (xvr_pose.h); 6: xvr_drr_spec.alpha_window + xvr_drr_alpha_window (clip_to_volume = 2); 5: xvr_drr_set_option / xvr_drr_get_option (the A/B switches are no longer getenv calls per launch); 4: volume_layout 2 + xvr_drr_pack_bricks (siddon forward); 3: xvr_drr_spec.volume_layout + xvr_drr_pack_ypairs; 2: xvr_sim_spec grew, camera-driven forwards, packed labels, xvr_pose.h */
 
 #define XVR_DRR_OK 0
 #define XVR_DRR_E_ARG (-1)     /* bad argument (null pointer, non-positive size, unsupported combo) */
@@ -225,6 +225,46 @@ int xvr_drr_siddon_backward(const float* volume, const float* mask, int D0, int 
                             float* grad_volume, float* grad_source, float* grad_target,
                             float* grad_raylen, void* workspace, size_t workspace_bytes, void* stream,
                             int slab_index, int slab_count);
+
+/*
+ * What a backward call would do for its voxel gradient, decided on the host without touching the GPU (works with no device
+ * present): the value of the one planner behind xvr_drr_trilinear_backward / xvr_drr_siddon_backward, for tests and tools.
+ *   siddon 0 / 1 picks the entry point; masked, want_volume, want_pose stand for mask, grad_volume, grad_target != NULL;
+ *   workspace_aligned for a non-NULL workspace on a 16-byte boundary; everything else is the backward's own argument.
+ * The options gather_splat, siddon_splat and siddon_gather_fast are read as the backward reads them.  Returns plan->error.
+ */
+enum {   /* xvr_drr_grad_plan.family: the kernel behind k_gather_prep / k_gather_cull */
+    XVR_DRR_GRAD_SCATTER = 0,            /* no gather: the re-marching scatter alone (fp32 atomics) */
+    XVR_DRR_GRAD_SIDDON_SPLAT,           /* k_siddon_splat<nx> */
+    XVR_DRR_GRAD_SIDDON_CELLS,           /* k_siddon_gather_cells + k_siddon_cells_to_voxels */
+    XVR_DRR_GRAD_SIDDON_MASK,            /* k_siddon_gather_mask */
+    XVR_DRR_GRAD_SIDDON_VOL2_FAST,       /* k_siddon_gather_vol2<true> */
+    XVR_DRR_GRAD_SIDDON_VOL2,            /* k_siddon_gather_vol2<false> */
+    XVR_DRR_GRAD_TRILINEAR_SPLAT_PX,     /* k_trilinear_splat_px<clip, mask> */
+    XVR_DRR_GRAD_TRILINEAR_GATHER_PX,    /* k_trilinear_gather_px<clip, mask> */
+    XVR_DRR_GRAD_TRILINEAR_SPLAT_B16,    /* k_trilinear_splat_b16 (+ the fine-sampling pair when fine_pair) */
+    XVR_DRR_GRAD_TRILINEAR_GATHER_TAB    /* k_trilinear_gather_tab */
+};
+typedef struct xvr_drr_grad_plan {
+    int64_t cmax_offset, cells_offset;   /* bytes into the workspace of the per-pose maxima / the per-cell scratch; -1: not used */
+    int32_t error;                       /* XVR_DRR_OK, or what the call returns before it launches anything (all else 0 then) */
+    int32_t noop;                        /* a slab after the first on a path that did the whole volume in call 0: nothing is launched */
+    int32_t siddon, gather, family;      /* gather: prep -> cull -> family run ahead of the scatter */
+    int32_t clip, mask, nx, exact;       /* template booleans: of the family (clip, mask, nx) and of the scatter tail (clip, mask, exact) */
+    int32_t V, bd[3];                    /* voxels per lane and axis; voxels per brick */
+    int32_t cmax_stride;
+    int32_t cells_wanted, cells, olo[3]; /* Siddon, non-exact map: the spec asks for the per-cell scratch; the workspace has it */
+    int32_t only_if_fine; float spv_limit; int32_t fine_pair;   /* fine_pair: a second cull + k_trilinear_gather_tab follow the splat */
+    int32_t bx0, bxn;                    /* brick planes along x of this slab */
+    int32_t later_slab;                  /* prep and cull stand from call 0 */
+    int32_t zero_flag_line, zero_brick_queue, zero_cmax, zero_xcd_queues;   /* the memsets ahead of the launches */
+    /* the scatter behind: a pose-only and / or a volume launch; guarded = volume runs only if the device flag says the gather
+       declined (and pose and volume are two launches, one otherwise); resident = that launch is sized to what is resident at once */
+    int32_t tail_pose, tail_volume, tail_guarded, tail_resident;
+} xvr_drr_grad_plan;
+int xvr_drr_voxel_gradient_plan(int siddon, int masked, int D0, int D1, int D2, int C, int B, int n, const xvr_drr_spec* spec,
+                                int want_volume, int want_pose, size_t workspace_bytes, int workspace_aligned, int slab_index,
+                                int slab_count, xvr_drr_grad_plan* plan);
 
 /*
  * Pose-side backward from the jacobian saved by a forward call: an elementwise product with the

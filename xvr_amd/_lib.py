@@ -95,6 +95,7 @@ EXPORTS = {
     "xvr_drr_get_option": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "xvr_drr_backward_workspace_bytes": ([_I, _I, _I, _I, _I], ctypes.c_size_t),
     "xvr_drr_siddon_backward_workspace_bytes": ([_I, _I, _I, _I, _I, ctypes.POINTER(CSpec)], ctypes.c_size_t),
+    "xvr_drr_voxel_gradient_plan": ([_I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(CSpec), _I, _I, ctypes.c_size_t, _I, _I, _I, _P], ctypes.c_int),
     "xvr_drr_trilinear_forward": (_FWD, ctypes.c_int),
     "xvr_drr_trilinear_backward": (_BWD, ctypes.c_int),
     "xvr_drr_siddon_forward": (_FWD, ctypes.c_int),

@@ -37,11 +37,6 @@ namespace {
 // transpose of the forward gather, up to summation order -- and it is deterministic.
 // =============================================================================================
 
-constexpr int CMAX_STRIDE = 32;   // words between two poses' max |c| (GatherArgs.cmax): one 128-byte line each
-// above this many samples of one pose per voxel the plain trilinear voxel gradient takes the fp32 table gather instead of the
-// fixed-point splat (the benchmark geometry has ~2, registration ~3; the "fine detector" case of tests/test_splat.py ~1500)
-constexpr float SPLAT_MAX_SAMPLES_PER_VOXEL = 48.f;
-
 __device__ __forceinline__ void cross3(const float* a, const float* b, float* o) {
     o[0] = a[1] * b[2] - a[2] * b[1];
     o[1] = a[2] * b[0] - a[0] * b[2];
@@ -396,8 +391,6 @@ __device__ __forceinline__ float linspace_sel(int k, int N, float near_, float f
 // 13 x 64 lanes x 8 B = 6.5 KiB of LDS per wavefront: 24 wavefronts per CU (6 per SIMD) fit in 160 KiB; measured flat from
 // (7 per SIMD, 11 rows) to (6, 13) and (5, 15), 5-8 % worse at (8, 9) and (4, 19)
 constexpr int TAB_ROWS = 13, TAB_WAVES = 6;
-constexpr unsigned TAB_R0_BITS = 24, TAB_N_BITS = 8;   // entry.x = first element of the run in q | count << 24; entry.y = alpha_k
-constexpr unsigned TAB_MAX_RAYS = 1u << TAB_R0_BITS;
 
 // two candidates against the lane's 2x2x2 block; signed distance of the sample from the block's first voxel per axis:
 // a (s + alpha d) + b - v folded into one fma (within an ulp of the forward's two-fma chain); the second voxel sits
@@ -1320,147 +1313,97 @@ __global__ __launch_bounds__(FAST ? 256 : 64) __attribute__((amdgpu_waves_per_eu
 
 }  // namespace
 
-// Set up the workspace and launch prep -> cull -> gather.  The caller launches the scatter fallback
+// Carry out a voxel-gradient plan (plan_voxel_gradient, drr_common.hiph -- every choice is made there): lay the workspace out,
+// zero what the plan says, launch prep -> cull -> the family's kernels.  The caller launches the scatter fallback
 // (with skip_unless_flag_gt = the returned flag) right behind it.
-int xvr_detail::launch_gather(bool siddon, const float* source, const float* target, const float* raylen, const float* grad_out,
-                  int B, int n, int gw, int D0, int D1, int D2, const xvr_drr_spec* sp, float* grad_volume,
-                  void* workspace, void* stream, unsigned** flag_out, int slab_index, int slab_count, const float* mask, int C,
-                  const int* siddon_olo, int siddon_splat) {
+int xvr_detail::launch_gather(const GradPlan& P, const float* source, const float* target, const float* raylen, const float* grad_out,
+                  int B, int n, int D0, int D1, int D2, const xvr_drr_spec* sp, const float* mask, int C, float* grad_volume,
+                  void* workspace, void* stream, unsigned** flag_out) {
     char* ws = static_cast<char*>(workspace);
+    const hipStream_t st = (hipStream_t)stream;
+    const int gw = sp->ray_grid_w;
     GatherArgs G = {};
-    const bool sid_splat = siddon && siddon_splat && !mask;
-    if (siddon && siddon_olo) {   // non-exact index map: per-cell octant sums in the scratch behind the regular workspace (the splat needs none)
-        if (!sid_splat) G.cells = reinterpret_cast<float*>(ws + align256(ws_bytes(B, n, D0, D1, D2)));
-        for (int k = 0; k < 3; ++k) G.olo[k] = siddon_olo[k];
-    }
-    G.sid_splat = sid_splat ? 1 : 0;
-    G.mask = mask;
-    G.C = C;
-    G.clip = (!siddon && sp->clip_to_volume == 1) ? 1 : 0;
-    // alphas any sample can take: [near, far] on the shared planes; under clip alpha = amin + u (amax - amin) with
-    // 0 <= amin, amin + span <= 1, i.e. within [min(0, near), max(1, far)]
-    G.cull_lo = G.clip ? fminf(0.f, sp->near_) : sp->near_;
-    G.cull_hi = G.clip ? fmaxf(1.f, sp->far_) : sp->far_;
-    if (siddon) { G.cull_lo = 0.f; G.cull_hi = 1.f; }
     G.source = source; G.target = target; G.raylen = raylen; G.gout = grad_out;
     G.B = B; G.n = n; G.W = gw; G.H = n / gw; G.D0 = D0; G.D1 = D1; G.D2 = D2; G.sp = *sp;
     G.flag = reinterpret_cast<unsigned*>(ws);
     G.poses = reinterpret_cast<PoseLattice*>(ws + ws_pose_off());
     G.q = reinterpret_cast<float4*>(ws + ws_q_off(B));
+    G.qs = P.siddon ? gw : gw + 1;
+    G.qn = P.siddon ? n : (n / gw) * (gw + 1);
     G.q2 = reinterpret_cast<float2*>(ws + ws_q2_off(B, n));
-    G.siddon = siddon ? 1 : 0;
-    G.qs = siddon ? gw : gw + 1;
-    G.qn = siddon ? n : (n / gw) * (gw + 1);
-    G.V = siddon ? 1 : 2;   // voxels per lane and axis
-    // trilinear without clip / per-channel masks: the brick-local fixed-point splat on 16^3 bricks (k_trilinear_splat_b16)
-    // unless the option "gather_splat" is 0 (A/B switch: the fp32 voxel-driven table gather)
-    const int splat_mode = xvr_detail::option(xvr_detail::OPT_GATHER_SPLAT);   // (2: the ray-major splat for every render, A/B)
-    const bool use_splat = splat_mode != 0;
-    const bool splat = !siddon && (splat_mode == 1 || splat_mode == 3) && sp->clip_to_volume != 1 && !mask;
-    if (siddon && (G.cells || G.mask)) { G.bd[0] = 4; G.bd[1] = 8; G.bd[2] = 8; }
-    else if (siddon) G.bd[0] = G.bd[1] = G.bd[2] = 8;
-    else {
-        if (G.clip || G.mask) G.V = 2;   // (the pixel-major kernel is written for 2x2x2 blocks)
-        G.bd[0] = G.bd[1] = G.bd[2] = 4 * G.V;
-    }
-    // clip_to_volume / per-channel mask: the ray-major splat unless XVR_DRR_GATHER_SPLAT=0 (A/B: the voxel-driven pixel-major gather)
-    const bool psplat = !siddon && use_splat && !splat && sp->n_points < 65536;   // (its list packs a step and a count into 16 bits each)
-    if (splat || psplat) {   // the poses' maxima behind q's used part ([B][2 n] float4, H (W + 1) = n + H used): a line per pose if it fits
-        G.cmax = reinterpret_cast<unsigned*>(G.q + (size_t)B * G.qn);
-        const int room = 4 * (n - n / gw);
-        G.cmax_stride = room < CMAX_STRIDE ? room : CMAX_STRIDE;
-    }
-    if (siddon && !G.cells && !G.mask) {   // per-pose "a ray is cut at alpha = 0 / 1" words behind q's used half ([B][2 n] float4, [B][n] used)
-        G.cmax = reinterpret_cast<unsigned*>(G.q + (size_t)B * n);
-        G.cmax_stride = 4 * n < CMAX_STRIDE ? 4 * n : CMAX_STRIDE;
-    }
-    if (psplat) G.bd[0] = G.bd[1] = G.bd[2] = 16;
-    if (splat || sid_splat) G.bd[0] = G.bd[1] = G.bd[2] = 16;
-    // gather_splat = 1: the splat, EXCEPT where a pose puts more than SPLAT_MAX_SAMPLES_PER_VOXEL samples on a voxel (decided on the
-    // device by k_gather_prep: the fp32 table gather then takes the whole launch); = 3: the splat whatever the sampling density
-    const int bd8[3] = {8, 8, 8}, bd16[3] = {16, 16, 16};
-    const bool auto_fp32 = splat && splat_mode == 1 && G.V == 2 && (long long)n / gw * (gw + 1) <= (long long)TAB_MAX_RAYS &&
-                           n_bricks(D0, D1, D2, bd16) + n_bricks(D0, D1, D2, bd8) <= n_bricks_max(D0, D1, D2);   // (both culls fit the workspace)
-    G.only_if_fine = auto_fp32 ? 0 : -1;
-    G.spv_limit = auto_fp32 ? SPLAT_MAX_SAMPLES_PER_VOXEL : 0.f;
-    if (sid_splat && G.cmax_stride < 2) return fail(XVR_DRR_E_UNSUPPORTED, "siddon splat: detector too small for its per-pose words");
+    G.siddon = P.siddon;
+    G.V = P.V;
+    for (int k = 0; k < 3; ++k) { G.bd[k] = P.bd[k]; G.olo[k] = P.olo[k]; }
     G.cull = reinterpret_cast<unsigned*>(ws + ws_cull_off(B, n));
     G.words = (B + 31) / 32;
     G.gvol = grad_volume;
+    G.mask = mask;
+    G.C = C;
+    G.clip = P.clip;
+    // alphas any sample can take: [near, far] on the shared planes; under clip alpha = amin + u (amax - amin) with
+    // 0 <= amin, amin + span <= 1, i.e. within [min(0, near), max(1, far)]; Siddon: [0, 1]
+    G.cull_lo = P.siddon ? 0.f : (P.clip ? fminf(0.f, sp->near_) : sp->near_);
+    G.cull_hi = P.siddon ? 1.f : (P.clip ? fmaxf(1.f, sp->far_) : sp->far_);
+    G.cells = P.cells ? reinterpret_cast<float*>(ws + P.cells_offset) : nullptr;
+    G.cmax = P.cmax_offset >= 0 ? reinterpret_cast<unsigned*>(ws + P.cmax_offset) : nullptr;
+    G.cmax_stride = P.cmax_stride;
+    G.sid_splat = P.family == XVR_DRR_GRAD_SIDDON_SPLAT;
+    G.only_if_fine = P.only_if_fine;
+    G.spv_limit = P.spv_limit;
+    G.bx0 = P.bx0;
+    G.bxn = P.bxn;
     *flag_out = G.flag;
-    // slab_index / slab_count (slab_count <= 1: the whole volume): the voxel gradient in `count` x slabs of whole brick planes, one backward call per slab
-    // (index 0 first; same arguments and workspace), so that the caller can hand slab i to a collective while slab i + 1 is computed.
-    // The brick splats take their slab's bricks; every other path does the whole volume in call 0 and nothing afterwards.
-    if (slab_count > 1 && (slab_index < 0 || slab_index >= slab_count)) return fail(XVR_DRR_E_ARG, "slab_index must lie in [0, slab_count)");
-    const bool later_slab = gather_slab_later(slab_index, slab_count);
-    const bool brick_splat = sid_splat || (!siddon && (psplat || (!G.clip && !G.mask && splat)));
-    const int nb0 = (D0 + 15) / 16;
-    G.bx0 = 0;
-    G.bxn = nb0;
-    if (slab_count > 1 && brick_splat) {
-        G.bx0 = (int)((long long)slab_index * nb0 / slab_count);
-        G.bxn = (int)((long long)(slab_index + 1) * nb0 / slab_count) - G.bx0;
-    }
-    if (later_slab && !brick_splat) return XVR_DRR_OK;
     const long long bricks = n_bricks(D0, D1, D2, G.bd);
-    if (bricks >= (1LL << 31)) return fail(XVR_DRR_E_UNSUPPORTED, "grid too large");
     hipError_t e = hipSuccess;
-    if (later_slab) e = hipMemsetAsync(G.flag + 1, 0, sizeof(unsigned), (hipStream_t)stream);   // (the brick queue; lattice flag, sticky words, poses and cull stand from call 0)
-    else {
-        e = hipMemsetAsync(G.flag, 0, 16, (hipStream_t)stream);
-        if (e == hipSuccess && G.cmax) e = hipMemsetAsync(G.cmax, 0, (size_t)B * G.cmax_stride * sizeof(unsigned), (hipStream_t)stream);
-    }
-    if (e == hipSuccess && sid_splat) e = hipMemsetAsync(G.flag + 16, 0, 8 * sizeof(unsigned), (hipStream_t)stream);   // (k_siddon_splat's per-XCD brick queues)
+    if (P.zero_brick_queue) e = hipMemsetAsync(G.flag + 1, 0, sizeof(unsigned), st);
+    if (P.zero_flag_line) e = hipMemsetAsync(G.flag, 0, 16, st);
+    if (e == hipSuccess && P.zero_cmax) e = hipMemsetAsync(G.cmax, 0, (size_t)B * G.cmax_stride * sizeof(unsigned), st);
+    if (e == hipSuccess && P.zero_xcd_queues) e = hipMemsetAsync(G.flag + 16, 0, 8 * sizeof(unsigned), st);
     if (e != hipSuccess) return fail(XVR_DRR_E_LAUNCH, hipGetErrorString(e));
-    if (!later_slab) {
-        hipLaunchKernelGGL(k_gather_prep, dim3((unsigned)((n + WG - 1) / WG), (unsigned)B), dim3(WG), 0,
-                           (hipStream_t)stream, G);
-        hipLaunchKernelGGL(k_gather_cull, dim3((unsigned)((bricks + WG / 32 - 1) / (WG / 32))), dim3(WG), 0,
-                           (hipStream_t)stream, G, (int)bricks);
+    if (!P.later_slab) {
+        hipLaunchKernelGGL(k_gather_prep, dim3((unsigned)((n + WG - 1) / WG), (unsigned)B), dim3(WG), 0, st, G);
+        hipLaunchKernelGGL(k_gather_cull, dim3((unsigned)((bricks + WG / 32 - 1) / (WG / 32))), dim3(WG), 0, st, G, (int)bricks);
     }
-    if (sid_splat) {
-        const bool nx = siddon_splat == 2;   // (2: a non-exact index map; 1: the exact one, A/B)
-        const void* kern = nx ? (const void*)k_siddon_splat<true> : (const void*)k_siddon_splat<false>;
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        const long long resident = (long long)per_cu * cus;
-        const dim3 grid((unsigned)(bricks < resident ? bricks : resident));
-        if (nx) hipLaunchKernelGGL(k_siddon_splat<true>, grid, dim3(256), 0, (hipStream_t)stream, G);
-        else hipLaunchKernelGGL(k_siddon_splat<false>, grid, dim3(256), 0, (hipStream_t)stream, G);
-    }
-    else if (siddon && G.cells) {
-        hipLaunchKernelGGL(k_siddon_gather_cells, dim3((unsigned)bricks), dim3(WG), 0, (hipStream_t)stream, G);
+    // persistent workgroups: as many as run at once (the occupancy the runtime reports x the CUs), never more than bricks
+    const auto persistent = [&](auto kern, long long resident) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)(bricks < resident ? bricks : resident)), dim3(256), 0, st, G);
+        return 0;
+    };
+    switch (P.family) {
+    case XVR_DRR_GRAD_SIDDON_SPLAT:
+        with_bools([&](auto NX) { return persistent(k_siddon_splat<NX()>, resident_workgroups<k_siddon_splat<NX()>>(256, 0, 2)); }, P.nx);
+        break;
+    case XVR_DRR_GRAD_SIDDON_CELLS: {
+        hipLaunchKernelGGL(k_siddon_gather_cells, dim3((unsigned)bricks), dim3(WG), 0, st, G);
         const long long nvox = (long long)D0 * D1 * D2;
-        hipLaunchKernelGGL(k_siddon_cells_to_voxels, dim3((unsigned)((nvox + WG - 1) / WG)), dim3(WG), 0, (hipStream_t)stream, G);
+        hipLaunchKernelGGL(k_siddon_cells_to_voxels, dim3((unsigned)((nvox + WG - 1) / WG)), dim3(WG), 0, st, G);
+        break;
     }
-    else if (siddon && G.mask) hipLaunchKernelGGL(k_siddon_gather_mask, dim3((unsigned)bricks), dim3(WG), 0, (hipStream_t)stream, G);
-    else if (siddon && xvr_detail::option(xvr_detail::OPT_SIDDON_GATHER_FAST)) {
+    case XVR_DRR_GRAD_SIDDON_MASK:
+        hipLaunchKernelGGL(k_siddon_gather_mask, dim3((unsigned)bricks), dim3(WG), 0, st, G);
+        break;
+    case XVR_DRR_GRAD_SIDDON_VOL2_FAST: {
         // four bricks in a row per workgroup, whichever axis the kernel picks for the rows: enough workgroups for the worst case
         const long long nb0 = (D0 + 7) / 8, nb1 = (D1 + 7) / 8, nb2 = (D2 + 7) / 8;
         const long long g0 = ((nb0 + 3) / 4) * nb1 * nb2, g1 = nb0 * ((nb1 + 3) / 4) * nb2, g2 = nb0 * nb1 * ((nb2 + 3) / 4);
         const long long groups = g0 > g1 ? (g0 > g2 ? g0 : g2) : (g1 > g2 ? g1 : g2);
-        hipLaunchKernelGGL(k_siddon_gather_vol2<true>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, G);
+        hipLaunchKernelGGL(k_siddon_gather_vol2<true>, dim3((unsigned)groups), dim3(256), 0, st, G);
+        break;
     }
-    else if (siddon) hipLaunchKernelGGL(k_siddon_gather_vol2<false>, dim3((unsigned)bricks), dim3(64), 0, (hipStream_t)stream, G);
-    else if (psplat) {
-        const void* kern = G.clip ? (G.mask ? (const void*)k_trilinear_splat_px<true, true> : (const void*)k_trilinear_splat_px<true, false>)
-                                  : (G.mask ? (const void*)k_trilinear_splat_px<false, true> : (const void*)k_trilinear_splat_px<false, false>);
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        const long long resident = (long long)per_cu * cus;
-        const dim3 grid((unsigned)(bricks < resident ? bricks : resident));
-        if (G.clip && G.mask) hipLaunchKernelGGL((k_trilinear_splat_px<true, true>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        else if (G.clip) hipLaunchKernelGGL((k_trilinear_splat_px<true, false>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        else if (G.mask) hipLaunchKernelGGL((k_trilinear_splat_px<false, true>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        else hipLaunchKernelGGL((k_trilinear_splat_px<false, false>), grid, dim3(256), 0, (hipStream_t)stream, G);
-    }
-    else if (G.clip && G.mask) hipLaunchKernelGGL((k_trilinear_gather_px<true, true>), dim3((unsigned)bricks), dim3(64), 0, (hipStream_t)stream, G);
-    else if (G.clip) hipLaunchKernelGGL((k_trilinear_gather_px<true, false>), dim3((unsigned)bricks), dim3(64), 0, (hipStream_t)stream, G);
-    else if (G.mask) hipLaunchKernelGGL((k_trilinear_gather_px<false, true>), dim3((unsigned)bricks), dim3(64), 0, (hipStream_t)stream, G);
-    else if (splat) {
-        if (auto_fp32 && !later_slab) {
+    case XVR_DRR_GRAD_SIDDON_VOL2:
+        hipLaunchKernelGGL(k_siddon_gather_vol2<false>, dim3((unsigned)bricks), dim3(64), 0, st, G);
+        break;
+    case XVR_DRR_GRAD_TRILINEAR_SPLAT_PX:
+        with_bools([&](auto CL, auto M) { return persistent(k_trilinear_splat_px<CL(), M()>, resident_workgroups<k_trilinear_splat_px<CL(), M()>>(256, 0, 2)); }, P.clip, P.mask);
+        break;
+    case XVR_DRR_GRAD_TRILINEAR_GATHER_PX:
+        with_bools([&](auto CL, auto M) {   // (clip and / or mask: the plain render never comes here)
+            if constexpr (CL() || M()) hipLaunchKernelGGL((k_trilinear_gather_px<CL(), M()>), dim3((unsigned)bricks), dim3(64), 0, st, G);
+            return 0;
+        }, P.clip, P.mask);
+        break;
+    case XVR_DRR_GRAD_TRILINEAR_SPLAT_B16:
+        if (P.fine_pair) {
             // the fine-sampling regime's pair behind the splat: cull on the table gather's 8^3 bricks (into the words behind the
             // splat's) and the gather itself, both of which return at once unless k_gather_prep raised word 3 of the flag line
             GatherArgs T = G;
@@ -1475,28 +1418,21 @@ int xvr_detail::launch_gather(bool siddon, const float* source, const float* tar
             // that compares the two dispatches bit for bit.)
             long long cull_wgs = (tb + WG / 32 - 1) / (WG / 32), tab_wgs = tb;
 #ifndef XVR_FULL_GRID_FALLBACKS
-            static const int tab_resident = [] {
-                int per_cu = 0, dev = 0, cus = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trilinear_gather_tab, 64, 0) != hipSuccess || per_cu < 1) per_cu = 4 * TAB_WAVES;
-                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-                return per_cu * cus;
-            }();
+            const long long tab_resident = resident_workgroups<k_trilinear_gather_tab>(64, 0, 4 * TAB_WAVES);
             if (tab_wgs > tab_resident) tab_wgs = tab_resident;
             if (cull_wgs > tab_resident / 4) cull_wgs = tab_resident / 4;   // (256-thread workgroups)
 #endif
-            hipLaunchKernelGGL(k_gather_cull, dim3((unsigned)cull_wgs), dim3(WG), 0, (hipStream_t)stream, T, (int)tb);
-            hipLaunchKernelGGL(k_trilinear_gather_tab, dim3((unsigned)tab_wgs), dim3(64), 0, (hipStream_t)stream, T);
+            hipLaunchKernelGGL(k_gather_cull, dim3((unsigned)cull_wgs), dim3(WG), 0, st, T, (int)tb);
+            hipLaunchKernelGGL(k_trilinear_gather_tab, dim3((unsigned)tab_wgs), dim3(64), 0, st, T);
         }
-        // persistent workgroups: as many as run at once (the occupancy the runtime reports x the CUs), never more than bricks
-        static const int resident = [] {
-            int per_cu = 0, dev = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trilinear_splat_b16, 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-            return per_cu * cus;
-        }();
-        hipLaunchKernelGGL(k_trilinear_splat_b16, dim3((unsigned)(bricks < resident ? bricks : resident)), dim3(256), 0, (hipStream_t)stream, G);
+        persistent(k_trilinear_splat_b16, resident_workgroups<k_trilinear_splat_b16>(256, 0, 2));
+        break;
+    case XVR_DRR_GRAD_TRILINEAR_GATHER_TAB:   // (qn <= TAB_MAX_RAYS: gather_usable)
+        hipLaunchKernelGGL(k_trilinear_gather_tab, dim3((unsigned)bricks), dim3(64), 0, st, G);
+        break;
+    default:
+        return fail(XVR_DRR_E_ARG, "launch_gather: the plan names no gather family");
     }
-    else hipLaunchKernelGGL(k_trilinear_gather_tab, dim3((unsigned)bricks), dim3(64), 0, (hipStream_t)stream, G);   // (qn <= TAB_MAX_RAYS: gather_usable)
     e = hipGetLastError();
     if (e != hipSuccess) return fail(XVR_DRR_E_LAUNCH, hipGetErrorString(e));
     return XVR_DRR_OK;
@@ -1534,11 +1470,21 @@ size_t xvr_drr_backward_workspace_bytes(int B, int n, int D0, int D1, int D2) {
 
 size_t xvr_drr_siddon_backward_workspace_bytes(int B, int n, int D0, int D1, int D2, const xvr_drr_spec* sp) {
     if (B <= 0 || n <= 0 || D0 <= 0 || D1 <= 0 || D2 <= 0 || !sp) return 0;
-    int olo[3];
-    const size_t base = ws_bytes(B, n, D0, D1, D2);
-    if (siddon_exact_geometry(sp) || !siddon_cell_offsets(sp, D0, D1, D2, olo)) return base;
-    if (xvr_detail::option(xvr_detail::OPT_SIDDON_SPLAT) >= 1 && siddon_map_in_bounds(sp, D0, D1, D2) && siddon_splat_detector_ok(sp, n)) return base;   // (the brick splat needs no per-cell scratch)
-    return align256(base) + siddon_cells_bytes(D0, D1, D2);
+    const char* msg = nullptr;
+    const size_t base = ws_bytes(B, n, D0, D1, D2);   // (the brick splat and the exact map need no per-cell scratch)
+    const GradPlan P = plan_voxel_gradient(grad_query(true, sp, B, n, D0, D1, D2, 1, false, false, true, 0, false, 0, 1), &msg);   // (asked without a workspace: what the spec wants)
+    return P.cells_wanted ? align256(base) + siddon_cells_bytes(D0, D1, D2) : base;
+}
+
+int xvr_drr_voxel_gradient_plan(int siddon, int masked, int D0, int D1, int D2, int C, int B, int n, const xvr_drr_spec* sp,
+                                int want_volume, int want_pose, size_t workspace_bytes, int workspace_aligned, int slab_index,
+                                int slab_count, xvr_drr_grad_plan* plan) {
+    if (!sp || !plan) return fail(XVR_DRR_E_ARG, "null pointer argument");
+    if (B <= 0 || n <= 0 || D0 < 2 || D1 < 2 || D2 < 2) return fail(XVR_DRR_E_ARG, "B, n must be positive and every volume dimension >= 2");
+    const char* msg = nullptr;
+    *plan = plan_voxel_gradient(grad_query(siddon != 0, sp, B, n, D0, D1, D2, C, masked != 0, want_pose != 0, want_volume != 0,
+                                           workspace_bytes, workspace_aligned != 0, slab_index, slab_count), &msg);
+    return plan->error ? fail(plan->error, msg) : XVR_DRR_OK;
 }
 
 }  // extern "C"

@@ -651,52 +651,25 @@ int xvr_drr_siddon_backward(const float* volume, const float* mask, int D0, int 
     fill_args(A, volume, mask, D0, D1, D2, C, source, target, raylen, B, n, sp);
     A.gout = grad_out; A.gvol = grad_volume; A.gsrc = grad_source; A.gtgt = grad_target; A.glen = grad_raylen;
     const size_t lds = mask ? (size_t)C * WG * sizeof(float) : 0;
-    // the gather needs the exact-geometry index map (voxel credited = voxel whose box holds the segment)
-    const bool exact_geom = siddon_exact_geometry(sp);
-    // (a non-exact index map gathers per plane cell into octant sums: needs the larger workspace of
-    //  xvr_drr_siddon_backward_workspace_bytes and a map that drifts by less than a voxel)
-    int olo[3] = {0, 0, 0};
-    const bool drift_ok = !exact_geom && siddon_cell_offsets(sp, D0, D1, D2, olo);
-    // option siddon_splat: 1 (default) = the ray-driven brick splat (k_siddon_splat, round 5) for non-exact maps; 2 = for the exact
-    // map too (A/B against k_siddon_gather_vol2); 0 = the round-2 per-cell gather (needs the larger workspace)
-    const int splat_opt = xvr_detail::option(xvr_detail::OPT_SIDDON_SPLAT);
-    // (the maps the forward's slab march serves -- points of the volume look up voxels inside it --, so that forward and voxel gradient
-    //  are one pair; a map that leaves the volume keeps the merge walk's family: per-cell gather or scatter)
-    const bool nx_in = !exact_geom && siddon_map_in_bounds(sp, D0, D1, D2);
-    const bool splat = !mask && siddon_splat_detector_ok(sp, n) && ((nx_in && splat_opt >= 1) || (exact_geom && splat_opt == 2));
-    const bool cells = drift_ok && !splat &&
-                       workspace_bytes >= align256(ws_bytes(B, n, D0, D1, D2)) + siddon_cells_bytes(D0, D1, D2);
-    // (a mask with a per-channel gradient: the one-voxel-per-lane gather that looks the upstream value up by the voxel's own
-    //  label -- exact geometry, where a segment's voxel is the voxel whose box holds it)
-    if (gvol && ((!mask && (exact_geom || cells || splat)) || (mask && exact_geom)) && gather_usable(sp, n, workspace, workspace_bytes, B, D0, D1, D2)) {
-        unsigned* flag = nullptr;
-        rc = launch_gather(true, source, target, raylen, grad_out, B, n, sp->ray_grid_w, D0, D1, D2, sp, grad_volume,
-                           workspace, stream, &flag, slab_index, slab_count, mask, C, exact_geom ? nullptr : olo,
-                           splat ? (exact_geom ? 1 : 2) : 0);
-        if (rc || gather_slab_later(slab_index, slab_count)) return rc;
-        RenderArgs Ap = A, Av = A;
-        Ap.gvol = nullptr;
-        Av.gsrc = nullptr; Av.gtgt = nullptr; Av.glen = nullptr;
-        Av.skip_unless_flag_gt = flag;
-        if (exact_geom && mask) {
-            if (gpose) { rc = launch(k_siddon<2, true, true, false, true>, Ap, lds, stream); if (rc) return rc; }
-            return launch(k_siddon<2, true, false, true, true>, Av, lds, stream);
-        }
-        if (exact_geom) {
-            if (gpose) { rc = launch(k_siddon<2, false, true, false, true>, Ap, 0, stream); if (rc) return rc; }
-            return launch(k_siddon<2, false, false, true, true>, Av, 0, stream);
-        }
-        if (gpose) { rc = launch(k_siddon<2, false, true, false, false>, Ap, 0, stream); if (rc) return rc; }
-        return launch(k_siddon<2, false, false, true, false>, Av, 0, stream);
-    }
-    if (gather_slab_later(slab_index, slab_count)) return XVR_DRR_OK;   // (the call for slab 0 did everything)
-#define SID_BWD2(M, E)                                                                  \
-    (gpose ? (gvol ? launch(k_siddon<2, M, true, true, E>, A, lds, stream)              \
-                   : launch(k_siddon<2, M, true, false, E>, A, lds, stream))            \
-           : launch(k_siddon<2, M, false, true, E>, A, lds, stream))
-#define SID_BWD(M) (exact_geom ? SID_BWD2(M, true) : SID_BWD2(M, false))
-    return mask ? SID_BWD(true) : SID_BWD(false);
-#undef SID_BWD
-#undef SID_BWD2
+    // (which voxel-driven family serves the index map, if any: plan_voxel_gradient)
+    // (the order this unit instantiates its backward kernels in is their order in the code object: pinned, so that changes of the
+    //  host code above leave the device code byte for byte what it was)
+    using K = void (*)(RenderArgs);
+    static const K order[] = {k_siddon<2, true, true, false, true>, k_siddon<2, true, false, true, true>, k_siddon<2, false, true, false, true>,
+                              k_siddon<2, false, false, true, true>, k_siddon<2, false, true, false, false>, k_siddon<2, false, false, true, false>,
+                              k_siddon<2, true, true, true, true>, k_siddon<2, true, true, true, false>, k_siddon<2, true, true, false, false>,
+                              k_siddon<2, true, false, true, false>, k_siddon<2, false, true, true, true>, k_siddon<2, false, true, true, false>};
+    (void)order;
+    const char* why = nullptr;
+    const GradPlan P = plan_voxel_gradient(grad_query(true, sp, B, n, D0, D1, D2, C, mask != nullptr, gpose, gvol, workspace ? workspace_bytes : 0,
+                                                      ws_is_aligned(workspace), slab_index, slab_count), &why);
+    if (P.error) return fail(P.error, why);
+    if (P.noop) return XVR_DRR_OK;
+    unsigned* flag = nullptr;
+    if (P.gather) rc = launch_gather(P, source, target, raylen, grad_out, B, n, D0, D1, D2, sp, mask, C, grad_volume, workspace, stream, &flag);
+    if (rc || !(P.tail_pose || P.tail_volume)) return rc;
+    return with_bools([&](auto M, auto E) {
+        return launch_tail<k_siddon<2, M(), true, false, E()>, k_siddon<2, M(), false, true, E()>, k_siddon<2, M(), true, true, E()>>(P, A, lds, flag, stream);
+    }, P.mask, P.exact);
 }
 }  // extern "C"

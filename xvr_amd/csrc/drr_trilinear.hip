@@ -731,33 +731,6 @@ __global__ __launch_bounds__(WG) void k_trilinear_bwd(RenderArgs A) {
     }
 }
 
-// The scatter kernel launched BEHIND a gather as its fallback (skip_unless_flag_gt set): as many workgroups as are resident at once,
-// walking the logical blocks grid-stride.  (XVR_FULL_GRID_FALLBACKS: the full grid, for the test that compares the two dispatches.)
-template <typename Kern>
-int launch_fallback(Kern kern, const RenderArgs& A, size_t lds_bytes, void* stream) {
-#ifdef XVR_FULL_GRID_FALLBACKS
-    return launch(kern, A, lds_bytes, stream);
-#else
-    const long long nblocks = (long long)A.B * A.blocks_per_pose;
-    if (nblocks >= (1LL << 31)) return fail(XVR_DRR_E_UNSUPPORTED, "grid too large");
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return fail(XVR_DRR_E_LAUNCH, hipGetErrorString(e));
-    }
-    // (asked of the runtime once per instantiation: at the dynamic LDS of its first launch, which only the masked variants use)
-    static const long long resident = [&] {
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), WG, lds_bytes) != hipSuccess || per_cu < 1) per_cu = 2;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        return (long long)per_cu * (cus >= 8 ? cus - cus % 8 : cus);   // a multiple of 8 workgroups: xcd_remap keeps an XCD on its own range
-    }();
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks < resident ? nblocks : resident)), dim3(WG), lds_bytes, (hipStream_t)stream, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(XVR_DRR_E_LAUNCH, hipGetErrorString(e));
-    return XVR_DRR_OK;
-#endif
-}
-
 }  // namespace
 
 extern "C" {
@@ -916,40 +889,27 @@ int xvr_drr_trilinear_backward(const float* volume, const float* mask, int D0, i
         return fail(XVR_DRR_E_ARG, "clip_to_volume == 2 needs spec.alpha_window (xvr_drr_alpha_window), and only it");
     if (sp->clip_to_volume == 2 && (mask || grad_target))
         return fail(XVR_DRR_E_UNSUPPORTED, "the alpha window's pose gradient comes from the jacobian (xvr_drr_backward_from_jac + xvr_drr_alpha_window_backward); one channel");
-    const bool clip = sp->clip_to_volume == 1;
     const size_t lds = mask ? (size_t)C * WG * sizeof(float) : 0;
-
-    // Voxel gradient by the atomic-free voxel-driven gather when the rays are a detector lattice: the per-lane flattened
-    // table kernel for the plain render, the pixel-major kernel under clip_to_volume and / or a mask; the scatter kernel
-    // stays as the general fallback and is launched right behind it, reading the lattice flag on the device (no host sync).
-    const bool gather = gvol && gather_usable(sp, n, workspace, workspace_bytes, B, D0, D1, D2);
-    if (gather_slab_later(slab_index, slab_count) && !gather) return XVR_DRR_OK;   // (the call for slab 0 did everything)
-    if (gather) {
-        unsigned* flag = nullptr;
-        rc = launch_gather(false, source, target, raylen, grad_out, B, n, sp->ray_grid_w, D0, D1, D2, sp, grad_volume,
-                           workspace, stream, &flag, slab_index, slab_count, mask, C);
-        if (rc || gather_slab_later(slab_index, slab_count)) return rc;
-        RenderArgs Ap = A, Av = A;
-        Ap.gvol = nullptr;
-        Av.gsrc = nullptr; Av.gtgt = nullptr; Av.glen = nullptr;
-        Av.skip_unless_flag_gt = flag;
-#define TRI_BWD_ONE(M, CL, GP, GV, ARGS) launch(k_trilinear_bwd<M, CL, GP, GV>, ARGS, lds, stream)
-#define TRI_BWD_PAIR(M, CL)                                                                   \
-        do {                                                                                  \
-            if (gpose) { rc = TRI_BWD_ONE(M, CL, true, false, Ap); if (rc) return rc; }       \
-            return launch_fallback(k_trilinear_bwd<M, CL, false, true>, Av, lds, stream);     \
-        } while (0)
-        if (mask) { if (clip) TRI_BWD_PAIR(true, true); else TRI_BWD_PAIR(true, false); }
-        if (clip) TRI_BWD_PAIR(false, true); else TRI_BWD_PAIR(false, false);
-#undef TRI_BWD_PAIR
-#undef TRI_BWD_ONE
-    }
-#define TRI_BWD(M, CL)                                                                         \
-    (gpose ? (gvol ? launch(k_trilinear_bwd<M, CL, true, true>, A, lds, stream)                \
-                   : launch(k_trilinear_bwd<M, CL, true, false>, A, lds, stream))              \
-           : launch(k_trilinear_bwd<M, CL, false, true>, A, lds, stream))
-    if (mask) return clip ? TRI_BWD(true, true) : TRI_BWD(true, false);
-    return clip ? TRI_BWD(false, true) : TRI_BWD(false, false);
-#undef TRI_BWD
+    // Voxel gradient by the atomic-free voxel-driven path when the rays are a detector lattice (the plan says which family); the
+    // scatter kernel stays as the general fallback and is launched right behind it, reading the lattice flag on the device.
+    // (the order this unit instantiates its backward kernels in is their order in the code object: pinned, so that changes of the
+    //  host code above leave the device code byte for byte what it was)
+    using K = void (*)(RenderArgs);
+    static const K order[] = {k_trilinear_bwd<true, true, true, false>, k_trilinear_bwd<true, true, false, true>, k_trilinear_bwd<true, false, true, false>,
+                              k_trilinear_bwd<true, false, false, true>, k_trilinear_bwd<false, true, true, false>, k_trilinear_bwd<false, true, false, true>,
+                              k_trilinear_bwd<false, false, true, false>, k_trilinear_bwd<false, false, false, true>, k_trilinear_bwd<true, true, true, true>,
+                              k_trilinear_bwd<true, false, true, true>, k_trilinear_bwd<false, true, true, true>, k_trilinear_bwd<false, false, true, true>};
+    (void)order;
+    const char* why = nullptr;
+    const GradPlan P = plan_voxel_gradient(grad_query(false, sp, B, n, D0, D1, D2, C, mask != nullptr, gpose, gvol, workspace ? workspace_bytes : 0,
+                                                      ws_is_aligned(workspace), slab_index, slab_count), &why);
+    if (P.error) return fail(P.error, why);
+    if (P.noop) return XVR_DRR_OK;
+    unsigned* flag = nullptr;
+    if (P.gather) rc = launch_gather(P, source, target, raylen, grad_out, B, n, D0, D1, D2, sp, mask, C, grad_volume, workspace, stream, &flag);
+    if (rc || !(P.tail_pose || P.tail_volume)) return rc;
+    return with_bools([&](auto M, auto CL) {
+        return launch_tail<k_trilinear_bwd<M(), CL(), true, false>, k_trilinear_bwd<M(), CL(), false, true>, k_trilinear_bwd<M(), CL(), true, true>>(P, A, lds, flag, stream);
+    }, P.mask, P.clip);
 }
 }  // extern "C"

@@ -124,7 +124,7 @@ def _workspace(lib, B, n, shape, device, cspec=None, cells=False):
                 ws = torch.empty((full + 3) // 4, device=device, dtype=torch.float32)
                 return ws, ws.numel() * 4
             except torch.OutOfMemoryError:
-                pass   # the smaller scratch below: the dispatcher falls back to the scatter
+                pass   # the smaller scratch below: the planner (csrc plan_voxel_gradient) falls back to the scatter
     key = (device, torch.cuda.current_stream(device).cuda_stream)   # one scratch per stream: concurrent backwards
     ws = _WORKSPACES.get(key)                                        # on two streams must not share it
     if ws is None or ws.numel() * 4 < nbytes:
